@@ -2,6 +2,7 @@
 """MM-PDE rollout benchmark (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cy-mmpde]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
 
 A *step* is one full MM-PDE forward step over the rank's trajectories (DMM
@@ -14,15 +15,23 @@ data-path collective).  --global-trajectories G fixes the job instead
 "strong").  value = node-updates/s of the whole job
 = trajectories_total * 2521 * K / max-over-ranks(time of the K timed steps).
 
-Also reported (rank 0):
+A plain run sets up, warms up, times the K steps, writes the last step's
+outputs if --dump-outputs DIR is given (DIR/pred.npy, and DIR/mesh.npy with a
+moving mesh; the inputs are seeded, so two builds compare output for output)
+and prints the result line.
+
+With --full also reported (rank 0), from timed passes of their own:
 * roofline: the dominant kernel (GNN edge stage, 12 launches per step) timed
   live with hipEvents recorded on its own stream around every launch, in a
   second timed pass of the same K steps run on ONE stream (the pass that sets
   `value` runs the fixed-grid model on a side stream beside the moving-mesh
   chain, where two edge kernels can share the GPU, and records no events);
   achieved = algorithmic FLOP per launch / mean launch time.
+* f32_exact: the K steps again with the exact-fp32 MFMA edge GEMM, and the
+  final state's difference from the main run.
 * cpu_baseline (N = 1 only): the CPU oracle (op-for-op restatement of the
   reference, oracle/refcpu.py) timed on a bounded sample on this host.
+* finite, knn_query_ties, node_stage_ms, hbm (cy-gnn / burgers-gnn).
 """
 from __future__ import annotations
 
@@ -42,6 +51,7 @@ METRIC = "MM-PDE rollout node-updates/sec, cylinder 2521-node mesh, 1/2/4/8 GPUs
 F32_MFMA_PEAK_TFLOPS = 157.3          # MI355X_MICROARCH.md: dense fp32 matrix peak
 F16_MFMA_PEAK_TFLOPS = 2516.6         # 256 CU x 4 SIMD x 1024 FLOP/clk x 2.4 GHz (~2.5 PF dense)
 HBM_PEAK_GBS = 8000.0
+DUMP_MAX_BYTES = 64 << 20             # --dump-outputs: all arrays together
 # counter records regenerated on the current kernels (tools/gpu_pmc.sh with
 # PMC_NAME=edge_pmc_r06; tools/gpu_configs.sh with STEP_HBM=...: tools/gpu_records.sh pmc:NAME)
 EDGE_PMC_RECORD = "edge_pmc_r06.json"
@@ -125,6 +135,27 @@ class EdgeTracer:
         return out
 
 
+def dump_outputs(out_dir, arrays, suffix=""):
+    """Write {name: device tensor} as out_dir/<name><suffix>.npy (float32 or
+    float64).  An array over its share of DUMP_MAX_BYTES is cut to a fixed,
+    seeded sample of its flattened elements (ascending positions)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype != torch.float64:
+            t = t.float()
+        t = t.cpu()
+        cap = share // t.element_size()
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(0)
+            pos = torch.randperm(t.numel(), generator=g)[:cap].sort().values
+            t = t.reshape(-1)[pos]
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), t.numpy())
+
+
 def cpu_baseline(kind, moving_mesh, seconds, side=48):
     """The CPU oracle (op-for-op restatement of the reference forward, unfused,
     brute-force kNN) on a bounded sample: 2 trajectories, repeated one-step
@@ -177,12 +208,21 @@ def main():
                     help="a FIXED number of trajectories for the whole job, sharded "
                          "contiguously across the ranks (strong scaling, BASELINE "
                          "configs[4]: 64 over 1/2/4/8 GPUs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed as "
+                         "DIR/<name>.npy: pred (the step's return) and, with a moving mesh, mesh")
+    ap.add_argument("--full", action="store_true",
+                    help="also run and report what the headline figure does not need: the "
+                         "traced roofline pass, the exact-fp32 run, the CPU baseline, the "
+                         "finite / kNN-tie checks and the HBM figures")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--edge-gemm", default="f16x3", choices=["f32", "f16x3"],
                     help="message_net_2 arithmetic (include/mmpde_hip.h MMPDE_EDGE_GEMM_*)")
     ap.add_argument("--no-f32-exact", action="store_true",
-                    help="skip the second, exact-fp32-MFMA timed run reported as f32_exact")
+                    help="with --full: skip the second, exact-fp32-MFMA timed run reported "
+                         "as f32_exact")
     ap.add_argument("--graph", nargs="?", const="streams", default=None, choices=["streams", "serial"],
                     help="replay hipGraph captures of the step instead of launching it eagerly: "
                          "'streams' (default) one graph per stage replayed on the stage's own "
@@ -245,8 +285,10 @@ def main():
     if args.priorities is not None:
         eng.set_priorities(args.priorities == "on")
     n_gnn = 2 if moving else 1
-    tracer = EdgeTracer(n_forwards=n_gnn * args.steps)
-    eng.trace_hook = tracer
+    tracer = None
+    if args.full:
+        tracer = EdgeTracer(n_forwards=n_gnn * args.steps)
+        eng.trace_hook = tracer
     u0 = u_all[:, 0].to(device).contiguous()
     n_t = t_len - 1
 
@@ -274,7 +316,8 @@ def main():
             run = eng.graph_step if graph else eng.step
             torch.cuda.synchronize(device)
             D.barrier(device)
-            tracer.active = trace
+            if tracer is not None:
+                tracer.active = trace
             t0 = time.perf_counter()
             for i in range(args.steps):
                 u = run(u, 1 + (args.warmup + i) % n_t)
@@ -282,47 +325,103 @@ def main():
             torch.cuda.synchronize(device)
             D.barrier(device)
             t1 = time.perf_counter()
-            tracer.active = False
+            if tracer is not None:
+                tracer.active = False
         return D.max_over_ranks(t1 - t0, device), u.clone()
 
     elapsed, u = timed_run(args.edge_gemm, False)
-    elapsed_traced, _ = timed_run(args.edge_gemm, True)
-    finite = bool(torch.isfinite(u).all())
-    exact = None
-    if not args.no_f32_exact and args.edge_gemm != "f32":
-        el32, u32 = timed_run("f32", False)
-        rel = ((u - u32).abs().max() / u32.abs().max().clamp_min(1e-30)).item()
-        exact = {"value": total * n_nodes * args.steps / el32,
-                 "ms_per_step": 1e3 * el32 / args.steps,
-                 "final_state_max_rel_diff_vs_main": rel}
-    launches = tracer.launch_times_ms()
-    ties = eng.knn_query_ties() if moving else 0
-    tracer.pool.close()
+    if args.dump_outputs:
+        # what the last timed step handed its caller: the prediction it returned and
+        # the moved mesh it left in eng.mesh (later passes overwrite both)
+        outs = {"pred": u}
+        if moving:
+            outs["mesh"] = eng.mesh
+        dump_outputs(args.dump_outputs, outs, f".rank{rank}" if world > 1 else "")
+    if args.full:
+        elapsed_traced, _ = timed_run(args.edge_gemm, True)
+        finite = bool(torch.isfinite(u).all())
+        exact = None
+        if not args.no_f32_exact and args.edge_gemm != "f32":
+            el32, u32 = timed_run("f32", False)
+            rel = ((u - u32).abs().max() / u32.abs().max().clamp_min(1e-30)).item()
+            exact = {"value": total * n_nodes * args.steps / el32,
+                     "ms_per_step": 1e3 * el32 / args.steps,
+                     "final_state_max_rel_diff_vs_main": rel}
+        launches = tracer.launch_times_ms()
+        ties = eng.knn_query_ties() if moving else 0
+        tracer.pool.close()
 
     if rank != 0:
         return
     n_local = (hi - lo) * n_nodes
-    k = gc.n
-    # Dominant kernel = the edge stage (message_net_2 over every edge + mean),
-    # 12 launches per step.  Algorithmic FLOP per launch:
-    # n nodes x k edges x 2 x 128 x 128.
-    edge_f = n_local * k * 2 * 128 * 128
-    tot_ms = sum(e for _, e, _ in launches)
-    node_ms = sum(nd for _, _, nd in launches)
-    nl = max(len(launches), 1)
-    launch_ms = tot_ms / nl
-    achieved = edge_f * len(launches) / max(tot_ms * 1e-3, 1e-12) / 1e12
-    # Peak of the arithmetic the kernel runs: f32 -> dense fp32 MFMA peak;
-    # f16x3 -> each fp32 product is three fp16 MFMA products, so the
-    # fp32-equivalent peak is the dense fp16 MFMA peak / 3.
-    peak = F32_MFMA_PEAK_TFLOPS if args.edge_gemm == "f32" else F16_MFMA_PEAK_TFLOPS / 3
-    traffic = None
-    pmc = os.path.join(ROOT, "profiles", EDGE_PMC_RECORD)   # tools/gpu_pmc.sh on this round's kernels
-    if os.path.exists(pmc):
-        with open(pmc) as f:
-            rec = json.load(f)
-        if rec.get("workload") == args.config and rec.get("nodes") == n_local:
-            traffic = rec.get("modes", {}).get(args.edge_gemm, {}).get("hbm_bytes_per_launch")
+
+    def full_figures(line):
+        """The --full part of the result line, from the passes run above."""
+        k = gc.n
+        # Dominant kernel = the edge stage (message_net_2 over every edge + mean),
+        # 12 launches per step.  Algorithmic FLOP per launch (SURVEY.md §8(d)):
+        # n nodes x k edges x 2 x 128 x 128.
+        edge_f = n_local * k * 2 * 128 * 128
+        tot_ms = sum(e for _, e, _ in launches)
+        node_ms = sum(nd for _, _, nd in launches)
+        nl = max(len(launches), 1)
+        launch_ms = tot_ms / nl
+        achieved = edge_f * len(launches) / max(tot_ms * 1e-3, 1e-12) / 1e12
+        # Peak of the arithmetic the kernel runs: f32 -> dense fp32 MFMA peak;
+        # f16x3 -> each fp32 product is three fp16 MFMA products, so the
+        # fp32-equivalent peak is the dense fp16 MFMA peak / 3.
+        peak = F32_MFMA_PEAK_TFLOPS if args.edge_gemm == "f32" else F16_MFMA_PEAK_TFLOPS / 3
+        traffic = None
+        pmc = os.path.join(ROOT, "profiles", EDGE_PMC_RECORD)   # tools/gpu_pmc.sh on this round's kernels
+        if os.path.exists(pmc):
+            with open(pmc) as f:
+                rec = json.load(f)
+            if rec.get("workload") == args.config and rec.get("nodes") == n_local:
+                traffic = rec.get("modes", {}).get(args.edge_gemm, {}).get("hbm_bytes_per_launch")
+        line["roofline"] = {
+            "kernel": ("gnn_edge_wave_kernel" if args.edge_gemm == "f16x3" else "gnn_edge_kernel")
+                      + " (message_net_2 over every edge + mean aggregation, one launch "
+                      "per GNN layer, 12 per step)",
+            "bound": "mfma", "achieved": achieved, "peak": peak,
+            "unit": "TFLOP/s", "frac": achieved / peak,
+            "traffic": traffic, "launch_ms": launch_ms, "launches": len(launches),
+            "flop_per_launch": edge_f,
+            "traced_pass_ms_per_step": 1e3 * elapsed_traced / args.steps,
+            "traced_pass_host_ms_per_step": 1e3 * host_s[(args.edge_gemm, True)] / args.steps,
+            "algorithmic_bytes_per_launch": n_local * (128 * 4 * 2 + k * 4 + 128 * 4),
+            "edge_gemm": args.edge_gemm,
+            "peak_basis": "dense fp32 MFMA" if args.edge_gemm == "f32" else
+                          "dense fp16 MFMA / 3 (three fp16 products per fp32 product)"}
+        line["node_stage_ms"] = node_ms / nl
+        line["finite"] = finite
+        if moving:
+            # kNN-30 queries with an exact fp64 distance tie (sklearn's order
+            # unpinned there), over every step this process ran
+            line["knn_query_ties"] = ties
+        if not moving:
+            # configs[2] is quoted against the scatter-add / HBM roofline: SURVEY.md
+            # §8(d)'s fused minimum of ~18.7 KB of HBM traffic per GNN node-update
+            # (per layer read + write h, the 2 KB of message_net_1 node halves, 35
+            # neighbour ids), against rocprofv3 FETCH/WRITE of the whole step
+            step_s = elapsed / args.steps
+            alg = n_local * 18.7e3
+            hbm = {"survey_fused_min_bytes_per_node_update": 18.7e3,
+                   "algorithmic_bytes_per_step": alg, "achieved": alg / step_s / 1e9,
+                   "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": alg / step_s / 1e9 / HBM_PEAK_GBS,
+                   "measured_bytes_per_step": None}
+            rec_path = os.path.join(ROOT, "profiles", STEP_HBM_RECORD)
+            if os.path.exists(rec_path):
+                with open(rec_path) as f:
+                    rec = json.load(f)
+                if rec.get("workload") == args.config and rec.get("nodes") == n_local:
+                    hbm["measured_bytes_per_step"] = rec["hbm_bytes_per_step"]
+                    hbm["measured_GBs"] = rec["hbm_bytes_per_step"] / step_s / 1e9
+            line["hbm"] = hbm
+        if exact is not None:
+            line["f32_exact"] = exact
+        if world == 1 and not args.no_cpu_baseline:
+            line["cpu_baseline"] = cpu_baseline(kind, moving, args.cpu_seconds, side or 48)
+
     line = {
         "metric": METRIC if kind == "cy" else METRIC.replace("cylinder 2521-node mesh",
                                                              f"Burgers {side}x{side} grid"),
@@ -356,50 +455,10 @@ def main():
                               "hipGraph replay of the step, every stage on one stream" if args.graph else
                               "eager, three HIP streams"),
                    "stream_priorities": bool(getattr(eng, "priorities", False))},
-        "roofline": {"kernel": ("gnn_edge_wave_kernel" if args.edge_gemm == "f16x3" else "gnn_edge_kernel")
-                               + " (message_net_2 over every edge + mean aggregation, one launch "
-                               "per GNN layer, 12 per step)",
-                     "bound": "mfma", "achieved": achieved, "peak": peak,
-                     "unit": "TFLOP/s", "frac": achieved / peak,
-                     "traffic": traffic, "launch_ms": launch_ms, "launches": len(launches),
-                     "flop_per_launch": edge_f,
-                     "traced_pass_ms_per_step": 1e3 * elapsed_traced / args.steps,
-                     "traced_pass_host_ms_per_step": 1e3 * host_s[(args.edge_gemm, True)] / args.steps,
-                     "algorithmic_bytes_per_launch": n_local * (128 * 4 * 2 + k * 4 + 128 * 4),
-                     "edge_gemm": args.edge_gemm,
-                     "peak_basis": "dense fp32 MFMA" if args.edge_gemm == "f32" else
-                                   "dense fp16 MFMA / 3 (three fp16 products per fp32 product)"},
-        "node_stage_ms": node_ms / nl,
         "host_issue_ms_per_step": 1e3 * host_s[(args.edge_gemm, False)] / args.steps,
-        "finite": finite,
     }
-    if moving:
-        # kNN-30 queries with an exact fp64 distance tie (sklearn's order
-        # unpinned there), over every step this process ran
-        line["knn_query_ties"] = ties
-    if not moving:
-        # configs[2] is quoted against the scatter-add / HBM roofline: SURVEY.md
-        # §8(d)'s fused minimum of ~18.7 KB of HBM traffic per GNN node-update
-        # (per layer read + write h, the 2 KB of message_net_1 node halves, 35
-        # neighbour ids), against rocprofv3 FETCH/WRITE of the whole step
-        step_s = elapsed / args.steps
-        alg = n_local * 18.7e3
-        hbm = {"survey_fused_min_bytes_per_node_update": 18.7e3,
-               "algorithmic_bytes_per_step": alg, "achieved": alg / step_s / 1e9,
-               "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": alg / step_s / 1e9 / HBM_PEAK_GBS,
-               "measured_bytes_per_step": None}
-        rec_path = os.path.join(ROOT, "profiles", STEP_HBM_RECORD)
-        if os.path.exists(rec_path):
-            with open(rec_path) as f:
-                rec = json.load(f)
-            if rec.get("workload") == args.config and rec.get("nodes") == n_local:
-                hbm["measured_bytes_per_step"] = rec["hbm_bytes_per_step"]
-                hbm["measured_GBs"] = rec["hbm_bytes_per_step"] / step_s / 1e9
-        line["hbm"] = hbm
-    if exact is not None:
-        line["f32_exact"] = exact
-    if world == 1 and not args.no_cpu_baseline:
-        line["cpu_baseline"] = cpu_baseline(kind, moving, args.cpu_seconds, side or 48)
+    if args.full:
+        full_figures(line)
     print(json.dumps(line), flush=True)
 
 

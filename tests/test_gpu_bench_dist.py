@@ -31,7 +31,7 @@ def test_bench_two_ranks_gloo(mode):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--dist-backend", "gloo", "--no-cpu-baseline", "--no-f32-exact"] + extra
+           "--dist-backend", "gloo", "--full", "--no-cpu-baseline", "--no-f32-exact"] + extra
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]

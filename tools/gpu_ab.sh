@@ -10,7 +10,7 @@ for so in $L/ab/*.so; do
   v=$(basename $so .so)
   cp $so $L/libmmpde_hip.so
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/ab/$v -o run -- \
-      python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-f32-exact --serial \
+      python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-f32-exact --serial \
       > gpurun_out/ab/$v.log 2>&1 || { tail -20 gpurun_out/ab/$v.log; exit 1; }
   f=$(find gpurun_out/ab/$v -name '*kernel_stats.csv' | head -1)
   echo "== $v: $(grep -o '"value": [0-9.e+]*' gpurun_out/ab/$v.log | head -1)"

@@ -12,7 +12,7 @@ for so in $L/abx/*.so; do
   v=$(basename $so .so)_$rep
   cp $so $L/libmmpde_hip.so
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$v -o run -- \
-      python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-f32-exact --serial \
+      python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-f32-exact --serial \
       > $O/$v.log 2>&1 || { tail -20 $O/$v.log; cp /tmp/libmmpde_hip.orig.so $L/libmmpde_hip.so; exit 1; }
   f=$(find $O/$v -name '*kernel_stats.csv' | head -1)
   echo "== $v: $(grep -o '"ms_per_step": [0-9.e+]*' $O/$v.log | head -1)"

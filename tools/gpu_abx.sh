@@ -17,7 +17,7 @@ for so in $L/${AB_DIR:-ab}/*.so; do
     timeout -k 10 200 python3 tools/gnn_out_dump.py $O/$v.pt > $O/$v.dump.log 2>&1 || { tail -20 $O/$v.dump.log; exit 1; }
   fi
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$v -o run -- \
-      python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-f32-exact --serial ${AB_BENCH_ARGS:-} \
+      python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-f32-exact --serial ${AB_BENCH_ARGS:-} \
       > $O/$v.log 2>&1 || { tail -20 $O/$v.log; exit 1; }
   f=$(find $O/$v -name '*kernel_stats.csv' | head -1)
   echo "== $v: $(grep -o '"value": [0-9.e+]*' $O/$v.log | head -1)"

@@ -15,13 +15,13 @@ echo "pytest rc=$rc"; tail -6 $O/gpu_tests.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail $O/smoke.log; exit 2; }
 echo "smoke ok"
-timeout -k 10 400 python -u bench.py > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 3; }
+timeout -k 10 400 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 3; }
 tail -1 $O/bench.json
-timeout -k 10 400 python -u bench.py --steps 10 --warmup 3 --global-trajectories 64 --no-cpu-baseline \
+timeout -k 10 400 python -u bench.py --full --steps 10 --warmup 3 --global-trajectories 64 --no-cpu-baseline \
     > $O/bench_g64.json 2> $O/bench_g64.err || { tail $O/bench_g64.err; exit 4; }
 tail -1 $O/bench_g64.json
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/closing_prof -o run -- \
-    python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-f32-exact --serial > $O/prof_bench.json 2>&1 \
+    python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-f32-exact --serial > $O/prof_bench.json 2>&1 \
     || { tail $O/prof_bench.json; exit 5; }
 f=$(find /tmp/closing_prof -name '*kernel_stats.csv' | head -1)
 cp $f $O/kernel_stats_serial.csv
@@ -36,7 +36,7 @@ for m in f16x3 f32; do
   tail -1 $O/train_$m.json
 done
 for cfg in cy-gnn burgers-mmpde burgers-gnn; do
-  timeout -k 10 300 python3 -u bench.py --config $cfg > $O/$cfg.bench.log 2>&1 || { tail -20 $O/$cfg.bench.log; exit 7; }
+  timeout -k 10 300 python3 -u bench.py --full --config $cfg > $O/$cfg.bench.log 2>&1 || { tail -20 $O/$cfg.bench.log; exit 7; }
   grep '^{' $O/$cfg.bench.log | tail -1 > $O/$cfg.bench.json
   echo "$cfg bench ok"
 done

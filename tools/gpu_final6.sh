@@ -16,7 +16,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -2 $O/gpu_tests.log
 timeout -k 10 300 python -u -c 'import __graft_entry__ as g; g.smoke()' > $O/smoke.log 2>&1 || { tail $O/smoke.log; exit 4; }
 tail -2 $O/smoke.log
-timeout -k 10 400 python -u bench.py > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 5; }
+timeout -k 10 400 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 5; }
 tail -1 $O/bench.json
 for m in f16x3 f32; do
   timeout -k 10 300 python3 tools/train_bench.py --edge-gemm $m --iters 20 --warmup 3 > $O/train_$m.json 2>&1 \

@@ -10,7 +10,7 @@ for b in 16 8; do
   for g in eager graph; do
     a=""; [ $g = graph ] && a="--graph"
     timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/t_${b}_$g -o run -- \
-        python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-f32-exact --batch $b $a \
+        python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-f32-exact --batch $b $a \
         > $O/b${b}_$g.json 2>&1 || { tail -20 $O/b${b}_$g.json; exit 3; }
   done
   echo "== B=$b: A = eager, B = graph"

@@ -4,9 +4,9 @@
 # point of 64 trajectories runs 8 per rank); host issue time per step beside each pass.
 set -u
 O=gpurun_out/gap; mkdir -p $O
-timeout -k 10 300 python -u bench.py --steps 20 --no-cpu-baseline --no-f32-exact > $O/plain.json 2> $O/plain.err || exit 3
-timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --no-cpu-baseline --no-f32-exact > $O/trun.json 2> $O/trun.err || exit 4
-for b in 8 4; do timeout -k 10 300 python -u bench.py --steps 20 --batch $b --no-cpu-baseline --no-f32-exact > $O/b$b.json 2> $O/b$b.err || exit 5; done
+timeout -k 10 300 python -u bench.py --full --steps 20 --no-cpu-baseline --no-f32-exact > $O/plain.json 2> $O/plain.err || exit 3
+timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --steps 20 --no-cpu-baseline --no-f32-exact > $O/trun.json 2> $O/trun.err || exit 4
+for b in 8 4; do timeout -k 10 300 python -u bench.py --full --steps 20 --batch $b --no-cpu-baseline --no-f32-exact > $O/b$b.json 2> $O/b$b.err || exit 5; done
 python - <<'PY'
 import json
 for f in ("plain", "trun", "b8", "b4"):

@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 for mode in f16x3 f32; do
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 ${PMC_TIMEOUT:-300} rocprofv3 --pmc $c --kernel-include-regex "$REGEX" \
-        --output-format csv -d "$OUT/$mode/$c" -o run -- python3 bench.py --steps 2 --warmup 1 \
+        --output-format csv -d "$OUT/$mode/$c" -o run -- python3 bench.py --full --steps 2 --warmup 1 \
         --no-cpu-baseline --no-f32-exact --edge-gemm $mode > "$OUT/$mode.$c.log" 2>&1
     rc=$?
     echo "pmc $mode $c rc=$rc"

@@ -20,7 +20,7 @@ node() {
   local O=gpurun_out/node_ctr
   mkdir -p $O
   export PMC_OUT=$O PMC_REGEX="gnn_node_kernel|gnn_embed_kernel" PMC_TIMEOUT=180 \
-         PMC_BENCH_ARGS="--steps 2 --warmup 1 --serial --no-f32-exact --no-cpu-baseline"
+         PMC_BENCH_ARGS="--full --steps 2 --warmup 1 --serial --no-f32-exact --no-cpu-baseline"
   bash tools/gpu_counters.sh \
     "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES" \
     "TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE" \

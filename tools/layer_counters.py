@@ -14,9 +14,9 @@ for f in glob.glob(os.path.join(d, "stats", "**", "*kernel_stats.csv"), recursiv
     for r in csv.DictReader(open(f)):
         stats[r["Name"]] = float(r["AverageNs"]) / 1e3
 out = {"source": "rocprofv3 --pmc, 3 separate passes (SQ/GRBM group, FETCH_SIZE, WRITE_SIZE), "
-                 "--kernel-include-regex layer kernels, bench.py --steps 2 --warmup 1 --serial "
+                 "--kernel-include-regex layer kernels, bench.py --full --steps 2 --warmup 1 --serial "
                  "--no-f32-exact (cy-mmpde, B=16, n=40336); durations from a --kernel-trace --stats "
-                 "pass of bench.py --steps 10 --warmup 3 --serial; tools/gpu_layer_counters.sh",
+                 "pass of bench.py --full --steps 10 --warmup 3 --serial; tools/gpu_layer_counters.sh",
        "derived_definitions": {
            "mfma_busy_frac": "SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8)",
            "valu_per_mfma": "SQ_INSTS_VALU / SQ_INSTS_MFMA (instructions, per dispatch)",
