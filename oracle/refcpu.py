@@ -151,9 +151,18 @@ def knn_query(src: torch.Tensor, qry: torch.Tensor, batches: int, k: int):
 # cannot take different sides in the two evaluations.
 RELU_PATTERN = None
 
+# Audit hook (tests only): a callable (sd, prefix, site, x, mask) sees every
+# ReLU site's pre-activation x next to the pattern about to be imposed on it
+# (None where RELU_PATTERN gives none), before the pattern is applied.  The
+# training tests use it in their float64 run, to compare a recorded pattern
+# with the sign of the float64 pre-activation instead of adopting it unseen.
+RELU_AUDIT = None
+
 
 def _relu(sd, p, site, x):
     m = RELU_PATTERN(sd, p, site) if RELU_PATTERN is not None else None
+    if RELU_AUDIT is not None:
+        RELU_AUDIT(sd, p, site, x.detach(), m)
     return torch.relu(x) if m is None else x * m.to(x.dtype)
 
 
