@@ -12,29 +12,27 @@
 // + (W1b h_j - w.(u,x,y)_j)); the reference's [E, 260] edge concat never
 // exists and the only per-edge work is one 128x128 GEMM per edge.
 //
-// Edge stage (the dominant kernel): persistent, one 768-thread workgroup per
-// CU walking a contiguous (XCD-local) range of 16-target tiles.  Waves 8-11 are
-// producers: for neighbour slot e of a tile they gather the 16 source rows of
-// b, form m = relu(a_i + b_j) in registers and store it to an LDS ring as the
-// exact per-lane A operand (F16X3: scaled fp16 hi/lo halves).  Waves 0-7 are
-// consumers: the two on one SIMD keep the same 32 output columns of W2 in
-// registers for the whole launch and split each round's slots (even / odd),
-// accumulating relu(. + b2) per target in registers (slot e of all 16 targets
-// shares one accumulator row, so no cross-lane traffic); after the tile's last
-// slot the odd-slot wave hands its sums to its partner through LDS, which
-// writes the mean.  Sharing columns rather than splitting them halves the
-// LDS operand reads (each slot is read by 4 waves, not 8).
-// A workgroup's waves land on SIMDs in the order 0,2,1,3 (MI355X_MICROARCH.md),
-// so waves w and w+4 share a SIMD: every SIMD pairs one MFMA stream with one
-// VALU/gather stream.  One barrier per round of 4 slots; producers run
-// ERING-1 rounds ahead, b rows are gathered two rounds before use.
+// Edge stage.  The inference forward's F16X3 edge stage is the one-wave-per-
+// SIMD kernel of edge_wave.hip (the hot edge path; launch_edge_stage forwards
+// to it).  This file holds the persistent "ring" kernel gnn_edge_kernel, which
+// serves the exact-fp32 mode (edge_gemm f32) and the training forward, where
+// it also writes the z2 > 0 relu mask the backward reuses: one 768-thread
+// workgroup per CU walking a contiguous (XCD-local) range of 16-target tiles.
+// Waves 8-11 are producers: for neighbour slot e of a tile they gather the 16
+// source rows of b, form m = relu(a_i + b_j) in registers and store it to an
+// LDS ring as the exact per-lane A operand (F16X3: scaled fp16 hi/lo halves).
+// Waves 0-7 are consumers: they multiply the slots by W2 (held in registers)
+// and accumulate relu(. + b2) per target in registers (slot e of all 16
+// targets shares one accumulator row, so no cross-lane traffic).  The layout
+// is described above the kernel.
 //
-// Node stage: 64 (or 32) rows per workgroup, 8 waves; every GEMM reads its
-// weight operand once per workgroup (wave w owns output column tile w for all
-// row blocks); activations are staged in LDS as MFMA operand images with
+// Node stage: 32 rows per workgroup, 8 waves; every GEMM reads its weight
+// operand once per workgroup (wave w owns output column tile w for both
+// 16-row blocks); activations are staged in LDS as MFMA operand images with
 // per-row power-of-two scales (F16X3), and (F16X3) each workgroup stores the
 // row maxima of its a', b' rows (layer.hpp).  No atomics: every output is
-// deterministic.
+// deterministic.  The embed kernel (embedding + layer 0's projections) shares
+// its staging and projection code.
 #include "common.hpp"
 #include <type_traits>
 #include "f16x3.hpp"
@@ -75,7 +73,6 @@ struct EdgeArgs {
     const char *pk;            // F16X3: this layer's packed images (column scales of W2)
     const float *rsc;          // F16X3: split scale of every target row (layer.hpp row maxima)
     float *mean;               // [n, 128]
-    uint64_t *stamps;          // profiling builds (PH bit 10): per-round s_memtime of block 0
     const int32_t *deg;        // RAGGED: in-degree of every target (nbr row entries past it are ignored)
     uint32_t *relu_mask;       // nullable: [n * k][4] bits z2 > 0 of every slot (training forward)
 };
@@ -90,31 +87,6 @@ struct RoundCtr {  // (tile j, round rd) of a running round index
     }
 };
 
-#ifndef MMPDE_EDGE_NC
-#define MMPDE_EDGE_NC 2
-#endif
-constexpr int EDGE_NC = MMPDE_EDGE_NC;
-#ifndef MMPDE_EDGE_NP
-#define MMPDE_EDGE_NP 1
-#endif
-constexpr int EDGE_NP = MMPDE_EDGE_NP;
-
-// PH: bit 0 produce, bit 1 consume (MFMA), bit 2 skip the gathers, bit 3 raise
-// the consumer waves' issue priority, bit 5 replace the producer's split by a
-// bare conversion, bit 6 store one ring piece in four (both timing only), bit 7
-// re-read the tile's a rows every round, bit 4 (NC == 2) split each round's slots
-// between the two consumer waves of a SIMD, which then own the same 32 output
-// columns (half the LDS operand reads of column-split waves), bit 10 record
-// per-round s_memtime stamps of block 0.  Bits other than 0, 1 and 4 are for
-// profiling builds (tools/ubench); production launches use EDGE_PH.
-#ifndef MMPDE_EDGE_PH
-#define MMPDE_EDGE_PH 27
-#endif
-constexpr int EDGE_PH = MMPDE_EDGE_PH;
-// relu_mask words need the SPLIT consumer layout (two waves per SIMD sharing 32
-// columns, cg < 4): other profiling builds reject relu_mask at launch
-constexpr bool kEdgeMaskOk = EDGE_NC == 2 && (EDGE_PH & 16);
-
 // Slot operand layout (v_mfma_f32_16x16x32_f16; F32: v_mfma_f32_16x16x4_f32): a
 // slot is the 16 x 128 message tile m[row][k] of one neighbour slot e of the
 // tile's 16 targets; lane l = 16 g + row holds 8 float4-sized pieces i < 8:
@@ -123,36 +95,42 @@ constexpr bool kEdgeMaskOk = EDGE_NC == 2 && (EDGE_PH & 16);
 //   F32   piece i: k = 16 i + 4 g + t (t < 4).
 // stored as 8 lane-contiguous 1 KB planes (8 KB per slot).
 //
-// Workgroup: 4 NC consumer waves + 4 producer waves (NC consumers per SIMD: a
-// workgroup's waves land on SIMDs in the order 0,2,1,3, so waves w, w + 4,
-// w + 8 share one).  Producer p builds slot ESL rd + p of round rd; consumer c
-// multiplies every slot by its 32 / NC output columns of W2 (held in
-// registers for the whole launch).  One barrier per round; producers run EPF
-// rounds ahead; b rows are gathered two rounds before use.
+// Workgroup: 8 consumer waves (0-7) + 4 producer waves (8-11).  A workgroup's
+// waves land on SIMDs in the order 0,2,1,3, so waves w, w + 4, w + 8 share one:
+// every SIMD holds two consumers and one producer.  Producer p builds slot
+// ESL rd + p of round rd, all 8 pieces of it.  The two consumers of a SIMD
+// keep the same 32 output columns of W2 in registers for the whole launch
+// (column tiles 2 cg, 2 cg + 1, cg = wave & 3) and split each round's slots:
+// wave w takes slots hs, hs + 2 with hs = w >> 2.  Sharing columns rather
+// than splitting them halves the LDS operand reads (each slot is read by 4
+// waves, not 8); after a tile's last round the odd-slot wave hands its sums to
+// its partner through LDS (xS), which writes the mean.  The consumers run at
+// raised issue priority (s_setprio 1): the MFMA stream goes first, the
+// producer's VALU and gathers fill in.  One barrier per round; producers run
+// EPF rounds ahead; b rows are gathered two rounds before use.
 // RAGGED: target i averages over its first deg[i] table entries (PyG / torch_scatter
 // mean over a variable in-degree: sum / max(deg, 1)); otherwise over all k.
-template <bool F16X3, int PH = EDGE_PH, int NC = EDGE_NC, int NP = EDGE_NP, bool RAGGED = false>
-__global__ __launch_bounds__(64 * (4 * NC + 4 * NP), 1) void gnn_edge_kernel(EdgeArgs p) {
-    constexpr bool SPLIT = NC == 2 && (PH & 16);
-    constexpr int CT = SPLIT ? 2 : 2 / NC;  // 16-column tiles per consumer wave
-    constexpr int SPW = SPLIT ? ESL / 2 : ESL;  // slots per consumer wave and round
-    constexpr int NPC = 8 / NP;  // float4 pieces of a slot lane per producer wave
-    constexpr int NCT = 256 * NC;  // consumer threads
+template <bool F16X3, bool RAGGED>
+__global__ __launch_bounds__(768, 1) void gnn_edge_kernel(EdgeArgs p) {
+    constexpr int CT = 2;         // 16-column tiles per consumer wave
+    constexpr int SPW = ESL / 2;  // slots per consumer wave and round
+    constexpr int NPC = 8;        // float4 pieces of a slot lane (all built by one producer wave)
+    constexpr int NCT = 512;      // consumer threads
     __shared__ float4 ring[ERING * ESL * SLOT4];  // [round % ERING][slot][plane][lane]
     __shared__ float a_lds[2][ET * NLDA];        // a rows of tile j in [j & 1]
     // F16X3: the split scales of tile j's rows in [j & 7] (staged with the a rows;
     // eight deep: the consumers read a tile's until one round after its last,
     // staging runs one tile ahead of the producers)
     __shared__ float rs_ring[8][ET];
-    // SPLIT: the odd-slot consumer's relu-sums of tile j, in [j & 1]
-    __shared__ float4 xS[SPLIT ? 2 * 4 * CT * 64 : 1];
+    // the odd-slot consumer's relu-sums of tile j, in [j & 1]
+    __shared__ float4 xS[2 * 4 * CT * 64];
     const int tid = threadIdx.x;
     // wave index in an SGPR: every role / slot / liveness test below is then a
     // scalar branch (a VGPR wave index made `live` divergent: exec-masked MFMA
     // blocks and accumulator copies at every slot)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int r = lane & 15, g = lane >> 4;
-    const bool producer = wave >= 4 * NC;
+    const bool producer = wave >= 8;
     int first, stride, nt;
     tile_schedule(blockIdx.x, gridDim.x, p.ntiles, first, stride, nt);
     const int k = p.k;
@@ -165,31 +143,26 @@ __global__ __launch_bounds__(64 * (4 * NC + 4 * NP), 1) void gnn_edge_kernel(Edg
 
     // a tiles (F16X3: scaled by their rows' split scales, |relu(a + b)| s < 2^11,
     // split8_relu_rtz): the consumer waves stage tile j + 1 while the producers
-    // work on tile j, 2 / NC float4 per consumer thread.
-    auto a_fetch = [&](int j, float4 *v, float *sv) {
-#pragma unroll
-        for (int u = 0; u < 2 / NC; ++u) {
-            const int e = tid + NCT * u, row = e >> 5, c4 = e & 31;
-            v[u] = *(const float4 *)(p.a + tile_row(j, row) * LH + 4 * c4);
-            sv[u] = F16X3 ? p.rsc[tile_row(j, row)] : 1.0f;
-        }
+    // work on tile j, one float4 per consumer thread (16 rows x 32 float4 =
+    // NCT).
+    static_assert(ET * LH / 4 == NCT, "a tile: one float4 per consumer thread");
+    auto a_fetch = [&](int j, float4 &v, float &sv) {
+        const int row = tid >> 5, c4 = tid & 31;
+        v = *(const float4 *)(p.a + tile_row(j, row) * LH + 4 * c4);
+        sv = F16X3 ? p.rsc[tile_row(j, row)] : 1.0f;
     };
-    auto a_store = [&](int j, const float4 *v, const float *sv) {
-#pragma unroll
-        for (int u = 0; u < 2 / NC; ++u) {
-            const int e = tid + NCT * u, row = e >> 5, c4 = e & 31;
-            float4 x = v[u];
-            if (F16X3) {
-                const float sc = sv[u];
-                x = make_float4(x.x * sc, x.y * sc, x.z * sc, x.w * sc);
-                if (c4 == 0) rs_ring[j & 7][row] = sc;
-            }
-            *(float4 *)(&a_lds[j & 1][row * NLDA + 4 * c4]) = x;
+    auto a_store = [&](int j, const float4 &v, const float &sc) {
+        const int row = tid >> 5, c4 = tid & 31;
+        float4 x = v;
+        if (F16X3) {
+            x = make_float4(x.x * sc, x.y * sc, x.z * sc, x.w * sc);
+            if (c4 == 0) rs_ring[j & 7][row] = sc;
         }
+        *(float4 *)(&a_lds[j & 1][row * NLDA + 4 * c4]) = x;
     };
     if (!producer && nt > 0) {
-        float4 v[2 / NC];
-        float sv[2 / NC];
+        float4 v;
+        float sv;
         a_fetch(0, v, sv);
         a_store(0, v, sv);
     }
@@ -197,16 +170,10 @@ __global__ __launch_bounds__(64 * (4 * NC + 4 * NP), 1) void gnn_edge_kernel(Edg
 
     if (producer) {
         // ------------------------------------------------------------ producer
-        // NP producers per slot (one per SIMD each): producer pidx builds
-        // pieces i0 .. i0 + NPC - 1 of slot pidx & 3 (F16X3: K steps
-        // i0 / 2 .. (i0 + NPC) / 2 - 1, hi and lo)
-        const int pidx = wave - 4 * NC;
-        if (PH & 2048) __builtin_amdgcn_s_setprio(2);  // profiling: producers first
-        const int pw = pidx & 3, i0 = (pidx >> 2) * NPC;
-        auto piece = [&](int i) {
-            const int ii = i0 + i;
-            return F16X3 ? 32 * (ii >> 1) + 8 * g + 4 * (ii & 1) : 16 * ii + 4 * g;
-        };
+        // producer wave 8 + pw builds slot pw of every round: pieces 0 .. 7
+        // (F16X3: K steps 0 .. 3, hi and lo)
+        const int pw = wave - 8;
+        auto piece = [&](int i) { return F16X3 ? 32 * (i >> 1) + 8 * g + 4 * (i & 1) : 16 * i + 4 * g; };
         float4 acur[NPC], bv0[NPC], bv1[NPC];
         float sc = 1.0f;  // F16X3: split scale of this lane's row (r) of the tile
         // every round issues the same loads (clamped addresses past the end or
@@ -240,84 +207,61 @@ __global__ __launch_bounds__(64 * (4 * NC + 4 * NP), 1) void gnn_edge_kernel(Edg
         // producer still writes its ring slot (nobody reads it unmasked; after
         // the last round the slot written is neither of the rounds still being
         // consumed).
-        auto body = [&](int it, float4 *bv, uint32_t &s_use, uint32_t &s_fill) {
+        auto body = [&](float4 *bv, uint32_t &s_use, uint32_t &s_fill) {
             // the index of round it + 3 is this round's first load: a later use
             // of a register only waits for the loads issued before it
             s_fill = src_of(c3);
             c3.next(rpt);
-            if (PH & 1) {
-                // the a rows of a tile are the same for all its rounds: read them
-                // from LDS once per tile (PH bit 7: every round)
-                if ((PH & 128) || cP.rd == 0) {
-                    const float *ar = &a_lds[cP.j & 1][r * NLDA];
+            // the a rows of a tile are the same for all its rounds: read them
+            // from LDS once per tile
+            if (cP.rd == 0) {
+                const float *ar = &a_lds[cP.j & 1][r * NLDA];
 #pragma unroll
-                    for (int i = 0; i < NPC; ++i) acur[i] = *(const float4 *)(ar + piece(i));
-                    if (F16X3) sc = rs_ring[cP.j & 7][r];
-                }
-                float4 *dst = ring + (slot * ESL + pw) * SLOT4 + i0 * 64 + lane;
-                uint32_t fold = 0;
+                for (int i = 0; i < NPC; ++i) acur[i] = *(const float4 *)(ar + piece(i));
+                if (F16X3) sc = rs_ring[cP.j & 7][r];
+            }
+            float4 *dst = ring + (slot * ESL + pw) * SLOT4 + lane;
 #pragma unroll
-                for (int h2 = 0; h2 < NPC / 2; ++h2) {
-                    const float4 &a0 = acur[2 * h2], &a1 = acur[2 * h2 + 1];
-                    const float4 &b0 = bv[2 * h2], &b1 = bv[2 * h2 + 1];
-                    float4 m0, m1;
-                    if (F16X3) {  // relu folded into the split (split8_relu_rtz)
-                        m0 = make_float4(fmaf(b0.x, sc, a0.x), fmaf(b0.y, sc, a0.y), fmaf(b0.z, sc, a0.z),
-                                         fmaf(b0.w, sc, a0.w));
-                        m1 = make_float4(fmaf(b1.x, sc, a1.x), fmaf(b1.y, sc, a1.y), fmaf(b1.z, sc, a1.z),
-                                         fmaf(b1.w, sc, a1.w));
-                        half8 hi, lo;
-                        if (PH & 32) {  // profiling: conversion only, no split (wrong values)
-                            const uint32_t w[4] = {
-                                __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(m0.x, m0.y)),
-                                __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(m0.z, m0.w)),
-                                __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(m1.x, m1.y)),
-                                __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(m1.z, m1.w))};
-                            hi = *(const half8 *)w;
-                            lo = hi;
-                        } else {
-                            split8_relu_rtz(m0, m1, hi, lo);
-                        }
-                        if (!(PH & 64) || h2 == 0) {
-                            dst[(2 * h2 + 0) * 64] = *(const float4 *)&hi;
-                            dst[(2 * h2 + 1) * 64] = *(const float4 *)&lo;
-                        } else {  // profiling: one store in four, the rest folded (kept live)
-                            const uint32_t *hw = (const uint32_t *)&hi, *lw = (const uint32_t *)&lo;
-                            fold ^= hw[0] ^ hw[1] ^ hw[2] ^ hw[3] ^ lw[0] ^ lw[1] ^ lw[2] ^ lw[3];
-                        }
-                    } else {
-                        m0 = make_float4(fmaxf(a0.x + b0.x, 0.0f), fmaxf(a0.y + b0.y, 0.0f),
-                                         fmaxf(a0.z + b0.z, 0.0f), fmaxf(a0.w + b0.w, 0.0f));
-                        m1 = make_float4(fmaxf(a1.x + b1.x, 0.0f), fmaxf(a1.y + b1.y, 0.0f),
-                                         fmaxf(a1.z + b1.z, 0.0f), fmaxf(a1.w + b1.w, 0.0f));
-                        dst[(2 * h2 + 0) * 64] = m0;
-                        dst[(2 * h2 + 1) * 64] = m1;
-                    }
+            for (int h2 = 0; h2 < NPC / 2; ++h2) {
+                const float4 &a0 = acur[2 * h2], &a1 = acur[2 * h2 + 1];
+                const float4 &b0 = bv[2 * h2], &b1 = bv[2 * h2 + 1];
+                float4 m0, m1;
+                if (F16X3) {  // relu folded into the split (split8_relu_rtz)
+                    m0 = make_float4(fmaf(b0.x, sc, a0.x), fmaf(b0.y, sc, a0.y), fmaf(b0.z, sc, a0.z),
+                                     fmaf(b0.w, sc, a0.w));
+                    m1 = make_float4(fmaf(b1.x, sc, a1.x), fmaf(b1.y, sc, a1.y), fmaf(b1.z, sc, a1.z),
+                                     fmaf(b1.w, sc, a1.w));
+                    half8 hi, lo;
+                    split8_relu_rtz(m0, m1, hi, lo);
+                    dst[(2 * h2 + 0) * 64] = *(const float4 *)&hi;
+                    dst[(2 * h2 + 1) * 64] = *(const float4 *)&lo;
+                } else {
+                    m0 = make_float4(fmaxf(a0.x + b0.x, 0.0f), fmaxf(a0.y + b0.y, 0.0f),
+                                     fmaxf(a0.z + b0.z, 0.0f), fmaxf(a0.w + b0.w, 0.0f));
+                    m1 = make_float4(fmaxf(a1.x + b1.x, 0.0f), fmaxf(a1.y + b1.y, 0.0f),
+                                     fmaxf(a1.z + b1.z, 0.0f), fmaxf(a1.w + b1.w, 0.0f));
+                    dst[(2 * h2 + 0) * 64] = m0;
+                    dst[(2 * h2 + 1) * 64] = m1;
                 }
-                if ((PH & 64) && fold == 0x9e3779b9u) dst[64] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             }
             cP.next(rpt);
             // gather the round two ahead into the registers just consumed
-            if (!(PH & 4)) gather(bv, s_use);
+            gather(bv, s_use);
             c2.next(rpt);
             slot = slot == ERING - 1 ? 0 : slot + 1;
-            if ((PH & 1024) && blockIdx.x == 0 && lane == 0 && it < 256)
-                p.stamps[2 * 256 * wave + 2 * it] = __builtin_amdgcn_s_memtime();
             __syncthreads();
-            if ((PH & 1024) && blockIdx.x == 0 && lane == 0 && it < 256)
-                p.stamps[2 * 256 * wave + 2 * it + 1] = __builtin_amdgcn_s_memtime();
         };
         for (int it = 0; it < NIT2; it += 2) {
-            body(it, bv0, s0, s1);
-            body(it + 1, bv1, s1, s0);
+            body(bv0, s0, s1);
+            body(bv1, s1, s0);
         }
     } else {
         // ------------------------------------------------------------ consumer
-        // this wave's output column tiles CT cg + cc (cc < CT); SPLIT: slots
+        // this wave's output column tiles CT cg + cc (cc < CT) and its slots
         // hs, hs + 2 of every round
-        const int cg = SPLIT ? (wave & 3) : wave;
-        const int hs = SPLIT ? (wave >> 2) : 0;
-        auto slotq = [&](int qq) { return SPLIT ? hs + 2 * qq : qq; };
+        const int cg = wave & 3;
+        const int hs = wave >> 2;
+        auto slotq = [&](int qq) { return hs + 2 * qq; };
         float4 wf[CT][8];
         half8 wh[CT][4], wl[CT][4];
         f32x4 bias[CT];  // accumulator initial value (message_net_2 bias, scaled; F16X3 per row)
@@ -350,7 +294,7 @@ __global__ __launch_bounds__(64 * (4 * NC + 4 * NP), 1) void gnn_edge_kernel(Edg
         f32x4 S[CT], Ssave[CT];
 #pragma unroll
         for (int cc = 0; cc < CT; ++cc) S[cc] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-        int pend = -1;  // SPLIT, even-slot wave: tile whose mean waits for the partner's sums
+        int pend = -1;  // even-slot wave: tile whose mean waits for the partner's sums
         // T: relu-sums in the scaled domain (F16X3: x sw[col] s[row], powers of
         // two); inv and the row scale undo it exactly before the division by the
         // degree
@@ -372,7 +316,7 @@ __global__ __launch_bounds__(64 * (4 * NC + 4 * NP), 1) void gnn_edge_kernel(Edg
             }
         };
         auto finish_pending = [&]() {  // after the barrier that follows the partner's store
-            if (SPLIT && pend >= 0) {
+            if (pend >= 0) {
 #pragma unroll
                 for (int cc = 0; cc < CT; ++cc) {
                     const float4 o = xS[(((pend & 1) * 4 + cg) * CT + cc) * 64 + lane];
@@ -384,7 +328,7 @@ __global__ __launch_bounds__(64 * (4 * NC + 4 * NP), 1) void gnn_edge_kernel(Edg
         };
         RoundCtr cC{0, 0};
         int slot = 0;
-        if (PH & 8) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);
         // The next half slot is read from LDS while the current one is
         // multiplied (the next round's first half too: that round was
         // completed by the previous barrier), and each slot's relu-sum update
@@ -438,13 +382,12 @@ __global__ __launch_bounds__(64 * (4 * NC + 4 * NP), 1) void gnn_edge_kernel(Edg
                     S[cc][t] += v;
                 }
             }
-            if constexpr (SPLIT) if (p.relu_mask) {
+            if (p.relu_mask) {
                 // the z2 > 0 bits the backward reuses (mmpde_gnn_edge_backward_sorted):
                 // ballots per (column tile cc, row t) cover rows 4 g + t, g < 4,
                 // 16 columns each; lane l < 16 stores row 4 (l >> 2) + (l & 3)'s
                 // word of this wave's 32 columns (CT = 2 tiles, cg < 4): one store
-                // per slot.  Builds without SPLIT reject relu_mask at launch
-                // (kEdgeMaskOk).
+                // per slot.
                 static_assert(CT == 2, "relu mask words take two column tiles per wave");
                 uint64_t bal[CT][4];
 #pragma unroll
@@ -464,8 +407,8 @@ __global__ __launch_bounds__(64 * (4 * NC + 4 * NP), 1) void gnn_edge_kernel(Edg
                 if (lane < 16 && row < p.n) p.relu_mask[(row * k + e) * 4 + cg] = word;
             }
         };
-        float4 xa[4], xb[4], an[2 / NC];
-        float asv[2 / NC];
+        float4 xa[4], xb[4], an;
+        float asv;
         int js = 1;  // next a tile to stage: stored in iteration js * rpt - 1 (the
                      // producers read it from iteration js * rpt), fetched up to two
                      // iterations earlier but after the previous store
@@ -480,7 +423,7 @@ __global__ __launch_bounds__(64 * (4 * NC + 4 * NP), 1) void gnn_edge_kernel(Edg
                     ++js;
                 }
             }
-            if (it >= EPF && it < NIT && (PH & 2)) {
+            if (it >= EPF && it < NIT) {
                 const float4 *base = ring + slot * ESL * SLOT4 + lane;
                 const float4 *nbase = ring + (slot == ERING - 1 ? 0 : slot + 1) * ESL * SLOT4 + lane;
                 if (it == EPF) rd_half(base + slotq(0) * SLOT4, 0, xa);
@@ -511,9 +454,7 @@ __global__ __launch_bounds__(64 * (4 * NC + 4 * NP), 1) void gnn_edge_kernel(Edg
                 }
                 sum_into(acc[SPW - 1], ESL * cC.rd + slotq(SPW - 1));
                 if (cC.rd == rpt - 1) {  // tile complete: mean = sum / degree (PyG mean)
-                    if (!SPLIT) {
-                        write_mean(cC.j, S);
-                    } else if (hs == 1) {  // hand the odd slots' sums to the partner wave
+                    if (hs == 1) {  // hand the odd slots' sums to the partner wave
 #pragma unroll
                         for (int cc = 0; cc < CT; ++cc)
                             xS[(((cC.j & 1) * 4 + cg) * CT + cc) * 64 + lane] =
@@ -529,16 +470,7 @@ __global__ __launch_bounds__(64 * (4 * NC + 4 * NP), 1) void gnn_edge_kernel(Edg
                 cC.next(rpt);
                 slot = slot == ERING - 1 ? 0 : slot + 1;
             }
-            if ((PH & 1024) && blockIdx.x == 0 && lane == 0 && it < 256)
-                p.stamps[2 * 256 * wave + 2 * it] = __builtin_amdgcn_s_memtime();
             __syncthreads();
-            if ((PH & 1024) && blockIdx.x == 0 && lane == 0 && it < 256)
-                p.stamps[2 * 256 * wave + 2 * it + 1] = __builtin_amdgcn_s_memtime();
-            if ((PH & 1024) && blockIdx.x == 0 && tid == 0 && (it == 0 || it == NIT2 - 1)) {
-                // shader clock vs the 100 MHz constant clock, first / last round
-                p.stamps[12 * 2 * 256 + (it ? 2 : 0)] = __builtin_amdgcn_s_memtime();
-                p.stamps[12 * 2 * 256 + (it ? 3 : 1)] = __builtin_amdgcn_s_memrealtime();
-            }
         }
         finish_pending();  // the loop ends with a barrier
     }
@@ -564,40 +496,27 @@ struct NodeArgs {
     const char *pk, *pkn;  // F16X3 images: this layer (U1, U2), next layer (W1)
     float *rmx_out;        // F16X3: row maxima of a', b' and their range records (layer.hpp)
     int64_t seg_n;         // rows per trajectory segment (range records)
-    int parts;             // mean = sum of `parts` buffers part_stride floats apart
-    int64_t part_stride;
-    // div_k > 0: the buffers hold neighbour sums (F16X3 wave edge kernel); the
-    // mean is their total / max(div_deg[row], 1), or / div_k without degrees
+    // div_k > 0: mean holds neighbour sums (F16X3 wave edge kernel); the mean
+    // is sum / max(div_deg[row], 1), or / div_k without degrees
     const int32_t *div_deg = nullptr;
     int div_k = 0;
     EdgeSplit split;       // units > 0: add the wave kernel's side blocks first
 };
 
 constexpr int NLD = 132;  // fp32 staging row stride (floats)
-#ifndef MMPDE_NODE_WPE
-#define MMPDE_NODE_WPE 4
-#endif
-constexpr int NODE_WPE = MMPDE_NODE_WPE;  // node / embed launch bounds: waves per SIMD
-// node / embed kernels: issue B operands one phase before their GEMMs instead
-// of just before them.  EARLY_U2: update_net_2's (dead bH / bM registers);
-// EARLY_B: the next projections' b' operands beside a' (measured: node
-// 50.6-51.1 vs 50.0-50.2 us, embed 45.2-45.4 vs 42.8-43.0 us with 4 spills;
-// off).  Same arithmetic either way.
-#ifndef MMPDE_NODE_EARLY_U2
-#define MMPDE_NODE_EARLY_U2 1
-#endif
-#ifndef MMPDE_NODE_EARLY_B
-#define MMPDE_NODE_EARLY_B 0
-#endif
-constexpr bool NODE_EARLY_U2 = MMPDE_NODE_EARLY_U2 != 0;
-// EARLY_M: update_net_1's mean-half operands beside the h-half ones at the
-// start, in the last layer's kernel (with the next projections it spills);
-// measured 31.9 against 31.3-31.4 us (profiles/r04_node_early_m_ab.log), so off
-#ifndef MMPDE_NODE_EARLY_M
-#define MMPDE_NODE_EARLY_M 0
-#endif
-constexpr bool NODE_EARLY_M = MMPDE_NODE_EARLY_M != 0;
-constexpr bool NODE_EARLY_B = MMPDE_NODE_EARLY_B != 0;
+constexpr int RB = 2;     // 16-row blocks per node / embed workgroup
+constexpr int ROWS = 16 * RB;
+constexpr int NODE_WPE = 4;  // node / embed launch bounds: waves per SIMD
+// Where the node / embed kernels issue their B (weight) operand loads; the
+// arithmetic is the same wherever they stand, the placements were measured:
+//   update_net_2's: one phase early, right after update_net_1's GEMMs (bH and
+//     bM are dead by then);
+//   the projections' b' operands: just before their GEMM, in proj_phase
+//     (beside a', one phase early: node 50.6-51.1 vs 50.0-50.2 us, embed
+//     45.2-45.4 vs 42.8-43.0 us with 4 spills);
+//   update_net_1's mean half: after the h-half GEMM (beside the h half at the
+//     start, last layer's kernel: 31.9 against 31.3-31.4 us,
+//     profiles/r04_node_early_m_ab.log; with the projections it spills).
 
 // Operand images in LDS, per 16-row block rb and K step s (1 KB units of 64
 // lanes x 16 B): F16X3 [rb][s (32-wide)][hi|lo] with lane (r, g) holding
@@ -605,8 +524,7 @@ constexpr bool NODE_EARLY_B = MMPDE_NODE_EARLY_B != 0;
 // prep(): rows of 128 fp32 values (src, row stride lds) -> image at k offset
 // kofs (multiple of 128) of an image KT wide; F16X3 scales each row by a power
 // of two (its max |x| -> [2^13, 2^14)) and records it in rs[row].  8 lanes per row.
-// nsum > 1: src is the first of nsum buffers sum_stride floats apart, added in
-// buffer order (the edge stage's per-part sums); div_k > 0: the total is then
+// div_k > 0: src holds neighbour sums; after the side blocks (split) they are
 // divided by the row's degree max(div_deg[row], 1), or by div_k (IEEE division:
 // torch_scatter's mean = sum / count).
 // The (row, part) item of prep's work index idx: a wave takes 8 rows x 8 parts,
@@ -631,43 +549,13 @@ __device__ __forceinline__ void prep_fetch(const float *src, int64_t lds, int64_
 // when global) -> the image (and copy, rs), after the optional side-block sums
 // and degree division (see prep).
 template <bool F16X3>
-__device__ __forceinline__ void prep_finish(float4 (&x)[4], const float *src, int64_t srow, int row, int part,
-                                            float4 *img, int KT, int kofs, float *rs, float *copy, int nsum,
-                                            int64_t sum_stride, const int32_t *div_deg, int div_k,
-                                            const EdgeSplit *split) {
-    const float *sp = src + srow * LH + 16 * part;
-    for (int ps = 1; ps < nsum; ++ps) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 y = *(const float4 *)(sp + ps * sum_stride + 4 * q);
-            x[q] = make_float4(x[q].x + y.x, x[q].y + y.y, x[q].z + y.z, x[q].w + y.w);
-        }
-    }
+__device__ __forceinline__ void prep_finish(float4 (&x)[4], int64_t srow, int row, int part, float4 *img,
+                                            int KT, int kofs, float *rs, float *copy, const int32_t *div_deg,
+                                            int div_k, const EdgeSplit *split) {
     if (split && split->units > 0) {
-        // side blocks of the units u of this row's segment whose first slot
-        // s0(u) = floor(u S / U) lies strictly inside the row's 16-row tile
-        // t (local): t k < s0(u) < (t + 1) k
-        const int64_t S = split->S, G = split->units, kk = split->k;
-        int64_t sg, q, lo, hi;
-        if ((uint64_t)(S + 1) * (uint64_t)(G + 1) + (uint64_t)split->seg_n < 0xffffffffull) {
-            // 32-bit divisions (wave-uniform test: a 64-bit one is a long
-            // instruction sequence, three per row here)
-            const uint32_t sn = (uint32_t)split->seg_n, r32 = (uint32_t)srow;
-            const uint32_t sg32 = r32 / sn, q32 = r32 - sg32 * sn, t = q32 / 16;
-            const uint32_t S32 = (uint32_t)S, G32 = (uint32_t)G, k32 = (uint32_t)kk;
-            sg = sg32;
-            q = q32;
-            lo = max(((t * k32 + 1) * G32 + S32 - 1) / S32, 1u);
-            hi = min(((t + 1) * k32 * G32 + S32 - 1) / S32 - 1, G32 - 1);
-        } else {
-            sg = srow / split->seg_n;
-            q = srow - sg * split->seg_n;
-            const int64_t t = q / 16;
-            lo = max(((t * kk + 1) * G + S - 1) / S, (int64_t)1);
-            hi = min(((t + 1) * kk * G + S - 1) / S - 1, G - 1);
-        }
-        for (int64_t w = lo; w <= hi; ++w) {
-            const float *q4 = split->side + ((sg * G + w) * 16 + (q & 15)) * 128 + 16 * part;
+        const SideUnits su = side_units(*split, srow);
+        for (int64_t w = su.lo; w <= su.hi; ++w) {
+            const float *q4 = split->side + ((su.sg * split->units + w) * 16 + (su.q & 15)) * 128 + 16 * part;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float4 y = *(const float4 *)(q4 + 4 * q);
@@ -712,12 +600,12 @@ __device__ __forceinline__ void prep_finish(float4 (&x)[4], const float *src, in
     }
 }
 
-template <bool F16X3, int ROWS>
+template <bool F16X3>
 __device__ __forceinline__ void prep(const float *src, int64_t lds, int64_t row0, int64_t nrows_valid,
                                      bool global, float4 *img, int KT, int kofs, float *rs,
-                                     float *copy = nullptr, int t0 = -1, int nthr = 512, int nsum = 1,
-                                     int64_t sum_stride = 0, const int32_t *div_deg = nullptr,
-                                     int div_k = 0, const EdgeSplit *split = nullptr) {
+                                     float *copy = nullptr, int t0 = -1, int nthr = 512,
+                                     const int32_t *div_deg = nullptr, int div_k = 0,
+                                     const EdgeSplit *split = nullptr) {
     // threads t0 .. t0 + nthr (default: the whole workgroup) share the rows
     for (int idx = t0 < 0 ? (int)threadIdx.x : (int)threadIdx.x - t0; idx < ROWS * 8; idx += nthr) {
         int row, part;
@@ -725,8 +613,7 @@ __device__ __forceinline__ void prep(const float *src, int64_t lds, int64_t row0
         float4 x[4];
         prep_fetch(src, lds, row0, nrows_valid, global, row, part, x);
         const int64_t srow = global ? min(row0 + row, nrows_valid - 1) : row;
-        prep_finish<F16X3>(x, src, srow, row, part, img, KT, kofs, rs, copy, nsum, sum_stride, div_deg, div_k,
-                           split);
+        prep_finish<F16X3>(x, srow, row, part, img, KT, kofs, rs, copy, div_deg, div_k, split);
     }
 }
 
@@ -752,7 +639,7 @@ struct BOps {
 };
 
 // acc[rb] += A(image rows, K steps s0 .. s0 + NS of an image KT wide) x B.
-template <bool F16X3, int RB, int NS>
+template <bool F16X3, int NS>
 __device__ __forceinline__ void gemm_tile(f32x4 *acc, const float4 *img, int KT, int s0,
                                           const BOps<F16X3, NS> &B, int lane) {
 #pragma unroll
@@ -797,7 +684,6 @@ struct RowValues {
 #pragma unroll
         for (int c = 0; c < MAX_TW; ++c) u[c] = c < tw ? uu[row * tw + c] : 0.0f;
     }
-    template <int ROWS>
     __device__ __forceinline__ void store(float (*rowv)[ROWS], const mmpde_gnn_scales &sc, int tid, int tw) const {
         rowv[0][tid] = t * sc.inv_tmax;
         rowv[1][tid] = x * sc.inv_lx;
@@ -833,15 +719,14 @@ struct W1C {
 // scales rs): a = W1[:, :128] h + w.(u, x, y) + w_t t + b1 (column tile wave),
 // b = W1[:, 128:256] h - w.(u, x, y) (column tile 8 + wave); the epilogue of
 // gnn_2d.py:53-57's message_net_1 split (see the file header).  rowv: per-row
-// (t, x, y, u_0 .. u_{tw-1}) planes of stride 16 RB.  bA: preloaded B operands of a.
-template <bool F16X3, int RB>
+// (t, x, y, u_0 .. u_{tw-1}) planes of stride ROWS.  bA: preloaded B operands of a.
+template <bool F16X3>
 __device__ __forceinline__ void proj_phase(const BOps<F16X3, F16X3 ? 4 : 8> &bA, const float4 *img,
                                            const float *rs, const float *rowv, const W1C &w,
                                            const char *pk, const float *w1r, int tw, int64_t row0,
                                            int64_t n, int64_t seg_n, float *a_out, float *b_out,
-                                           float *rmx_out, uint32_t *arrived, int wave, int lane,
-                                           const BOps<F16X3, F16X3 ? 4 : 8> *bBpre = nullptr) {
-    constexpr int ROWS = 16 * RB, S1 = F16X3 ? 4 : 8;
+                                           float *rmx_out, uint32_t *arrived, int wave, int lane) {
+    constexpr int S1 = F16X3 ? 4 : 8;
     const int col = 16 * wave + (lane & 15), g = lane >> 4;
     f32x4 aA[RB], aB[RB];
 #pragma unroll
@@ -864,15 +749,13 @@ __device__ __forceinline__ void proj_phase(const BOps<F16X3, F16X3 ? 4 : 8> &bA,
         for (int c = 1; c < tw; ++c) node += w1r[256 + c] * rowv[(3 + c) * ROWS + lr];
         return node + w.dx * rowv[ROWS + lr] + w.dy * rowv[2 * ROWS + lr];
     };
-    gemm_tile<F16X3, RB, S1>(aA, img, 128, 0, bA, lane);
+    gemm_tile<F16X3, S1>(aA, img, 128, 0, bA, lane);
     {
-        if (bBpre) {  // operands of b preloaded (the weight-stationary node kernel)
-            gemm_tile<F16X3, RB, S1>(aB, img, 128, 0, *bBpre, lane);
-        } else {
-            BOps<F16X3, S1> bB;
-            bB.load(pk + kPkW1, 4, 8 + wave, 0, w1r, 128, lane);
-            gemm_tile<F16X3, RB, S1>(aB, img, 128, 0, bB, lane);
-        }
+        // b's operands are loaded here, not beside a's a phase early (measured
+        // slower, see the note at NODE_WPE)
+        BOps<F16X3, S1> bB;
+        bB.load(pk + kPkW1, 4, 8 + wave, 0, w1r, 128, lane);
+        gemm_tile<F16X3, S1>(aB, img, 128, 0, bB, lane);
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
 #pragma unroll
@@ -976,7 +859,7 @@ __device__ __forceinline__ void proj_phase(const BOps<F16X3, F16X3 ? 4 : 8> &bA,
     }
 }
 
-// Profiling builds only (tools/ubench/node_ubench with -DMMPDE_NODE_STAMPS):
+// Profiling builds only (tools/ubench/node_phases, built with -DMMPDE_NODE_STAMPS):
 // thread 0 of every workgroup records the 100 MHz real-time clock (one clock
 // for the whole chip) at the phase boundaries into g_node_stamps[block][8]
 // (vector stores).
@@ -992,10 +875,9 @@ __device__ uint64_t *g_node_stamps;
     } while (0)
 #endif
 
-template <bool NEXT, bool F16X3, int RB>
+template <bool NEXT, bool F16X3>
 __global__ __launch_bounds__(512, NODE_WPE) void gnn_node_kernel(NodeArgs p) {
     NODE_STAMP(0);
-    constexpr int ROWS = 16 * RB;
     __shared__ float4 img[RB * 16 * 64];        // operand image, K = 256 (h | mean), then 128
     __shared__ float stage[ROWS * NLD];         // fp32 v, then h'
     __shared__ float hres[ROWS * NLD];          // fp32 h (residual)
@@ -1024,30 +906,21 @@ __global__ __launch_bounds__(512, NODE_WPE) void gnn_node_kernel(NodeArgs p) {
     const float *w1r = NEXT ? p.w1n + (int64_t)col * p.ld_w1n : nullptr;
     W1C w1c;
     if (NEXT) w1c.load<F16X3>(w1r, p.b1n, p.pkn, col, tw);
-    // weight operands of update_net_1 / _2 loaded first: their latency hides
-    // behind the activation staging
-    // (RB >= 4: all three up front; smaller tiles run several workgroups per
-    // CU, whose overlap hides the latency, so they load just before use)
-    constexpr bool PRE = RB >= 4;
+    // update_net_1's h-half weight operands loaded first: their latency hides
+    // behind the activation staging.  The others load just before use (a
+    // 32-row tile runs several workgroups per CU, whose overlap hides the
+    // latency).
     BOps<F16X3, S1> bH, bM, bU2;
     bH.load(p.pk + kPkU1, 8, wave, 0, wu1, 0, lane);
-    if (PRE || (NODE_EARLY_M && !NEXT)) bM.load(p.pk + kPkU1, 8, wave, S1, wu1, 128, lane);
-    if (PRE) {
-        bU2.load(p.pk + kPkU2, 4, wave, 0, wu2, 0, lane);
-    }
-    if (tid < ROWS) rv.store<ROWS>(rowv, p.sc, tid, tw);
+    if (tid < ROWS) rv.store(rowv, p.sc, tid, tw);
 
     NODE_STAMP(1);
     // ---- [h | mean] -> image (K = 256)
-    if constexpr (ROWS * 8 <= 256) {  // h on waves 0-3, mean on waves 4-7 at once
-        if (tid < 256) prep<F16X3, ROWS>(p.h, LH, row0, p.n, true, img, 256, 0, rs[0], hres, 0, 256);
-        else prep<F16X3, ROWS>(p.mean, LH, row0, p.n, true, img, 256, 128, rs[1], nullptr, 256, 256, p.parts,
-                               p.part_stride, p.div_deg, p.div_k, &p.split);
-    } else {
-        prep<F16X3, ROWS>(p.h, LH, row0, p.n, true, img, 256, 0, rs[0], hres);
-        prep<F16X3, ROWS>(p.mean, LH, row0, p.n, true, img, 256, 128, rs[1], nullptr, -1, 512, p.parts,
-                          p.part_stride, p.div_deg, p.div_k, &p.split);
-    }
+    // h on waves 0-3, mean on waves 4-7 at once (ROWS * 8 = 256 items each:
+    // one per thread)
+    if (tid < 256) prep<F16X3>(p.h, LH, row0, p.n, true, img, 256, 0, rs[0], hres, 0, 256);
+    else prep<F16X3>(p.mean, LH, row0, p.n, true, img, 256, 128, rs[1], nullptr, 256, 256, p.div_deg,
+                     p.div_k, &p.split);
     __syncthreads();
     NODE_STAMP(2);
 
@@ -1056,12 +929,12 @@ __global__ __launch_bounds__(512, NODE_WPE) void gnn_node_kernel(NodeArgs p) {
         f32x4 aH[RB], aM[RB];
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) aH[rb] = aM[rb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-        gemm_tile<F16X3, RB, S1>(aH, img, 256, 0, bH, lane);
-        if (!PRE && !(NODE_EARLY_M && !NEXT)) bM.load(p.pk + kPkU1, 8, wave, S1, wu1, 128, lane);
-        gemm_tile<F16X3, RB, S1>(F16X3 ? aM : aH, img, 256, S1, bM, lane);
+        gemm_tile<F16X3, S1>(aH, img, 256, 0, bH, lane);
+        bM.load(p.pk + kPkU1, 8, wave, S1, wu1, 128, lane);
+        gemm_tile<F16X3, S1>(F16X3 ? aM : aH, img, 256, S1, bM, lane);
         // update_net_2's operands issued now (bH / bM are dead): in flight over
         // this epilogue, the operand prep and its two barriers
-        if (!PRE && NODE_EARLY_U2) bU2.load(p.pk + kPkU2, 4, wave, 0, wu2, 0, lane);
+        bU2.load(p.pk + kPkU2, 4, wave, 0, wu2, 0, lane);
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
 #pragma unroll
@@ -1075,22 +948,20 @@ __global__ __launch_bounds__(512, NODE_WPE) void gnn_node_kernel(NodeArgs p) {
     }
     NODE_STAMP(3);
     __syncthreads();
-    prep<F16X3, ROWS>(stage, NLD, 0, ROWS, false, img, 128, 0, rs[2]);
+    prep<F16X3>(stage, NLD, 0, ROWS, false, img, 128, 0, rs[2]);
     __syncthreads();
     NODE_STAMP(4);
 
     // ---- update_net_2 + residual + BatchNorm(eval)
-    BOps<F16X3, S1> bA, bB;
+    BOps<F16X3, S1> bA;
     {
         f32x4 acc[RB];
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) acc[rb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-        if (!PRE && !NODE_EARLY_U2) bU2.load(p.pk + kPkU2, 4, wave, 0, wu2, 0, lane);
-        gemm_tile<F16X3, RB, S1>(acc, img, 128, 0, bU2, lane);
-        // next layer's message_net_1 operands of a' (column tile wave), and of
-        // b' with NODE_EARLY_B (both in flight over the epilogue and the prep)
+        gemm_tile<F16X3, S1>(acc, img, 128, 0, bU2, lane);
+        // next layer's message_net_1 operands of a' (column tile wave), in
+        // flight over the epilogue and the prep
         if (NEXT) bA.load(p.pkn + kPkW1, 4, wave, 0, w1r, 0, lane);
-        if (NEXT && NODE_EARLY_B) bB.load(p.pkn + kPkW1, 4, 8 + wave, 0, w1r, 128, lane);
         const bool full = row0 + ROWS <= p.n;
         float *hp = p.h_out + (row0 + 4 * g) * LH + col;
 #pragma unroll
@@ -1110,12 +981,12 @@ __global__ __launch_bounds__(512, NODE_WPE) void gnn_node_kernel(NodeArgs p) {
     NODE_STAMP(5);
     if constexpr (NEXT) {
         __syncthreads();
-        prep<F16X3, ROWS>(stage, NLD, 0, ROWS, false, img, 128, 0, rs[3]);
+        prep<F16X3>(stage, NLD, 0, ROWS, false, img, 128, 0, rs[3]);
         __syncthreads();
         NODE_STAMP(6);
         // ---- next layer's message_net_1 node halves
-        proj_phase<F16X3, RB>(bA, img, rs[3], &rowv[0][0], w1c, p.pkn, w1r, tw, row0, p.n, p.seg_n,
-                              p.a_out, p.b_out, p.rmx_out, &rng_arrived, wave, lane, NODE_EARLY_B ? &bB : nullptr);
+        proj_phase<F16X3>(bA, img, rs[3], &rowv[0][0], w1c, p.pkn, w1r, tw, row0, p.n, p.seg_n,
+                              p.a_out, p.b_out, p.rmx_out, &rng_arrived, wave, lane);
     }
     NODE_STAMP(7);
 }
@@ -1141,9 +1012,8 @@ struct EmbedArgs {
     int64_t seg_n;         // rows per trajectory segment (range records)
 };
 
-template <bool F16X3, int RB>
+template <bool F16X3>
 __global__ __launch_bounds__(512, NODE_WPE) void gnn_embed_kernel(EmbedArgs p) {
-    constexpr int ROWS = 16 * RB;
     constexpr int S1 = F16X3 ? 4 : 8;
     __shared__ float4 img[RB * 8 * 64];   // K = 128 operand image
     __shared__ float stage[ROWS * NLD];   // fp32 z, then h0
@@ -1202,7 +1072,7 @@ __global__ __launch_bounds__(512, NODE_WPE) void gnn_embed_kernel(EmbedArgs p) {
     const float zb = e.b0[c];
     BnAffine bn1;
     bn1.set(e.bn1_rm[c], e.bn1_rv[c], e.bn1_w[c], e.bn1_b[c], e.eps);
-    if (tid < ROWS) rv.store<ROWS>(rowv, p.sc, tid, tw);
+    if (tid < ROWS) rv.store(rowv, p.sc, tid, tw);
     __syncthreads();
     for (int row = tid >> 7; row < ROWS; row += 4) {
         float v = zb + zw0 * rowv[3][row];
@@ -1211,24 +1081,23 @@ __global__ __launch_bounds__(512, NODE_WPE) void gnn_embed_kernel(EmbedArgs p) {
         stage[row * NLD + c] = fmaxf(bn1(v), 0.0f);
     }
     __syncthreads();
-    prep<F16X3, ROWS>(stage, NLD, 0, ROWS, false, img, 128, 0, rsz);
+    prep<F16X3>(stage, NLD, 0, ROWS, false, img, 128, 0, rsz);
     __syncthreads();
-    BOps<F16X3, S1> bA, bB;
+    BOps<F16X3, S1> bA;
     {
         f32x4 acc[RB];
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) acc[rb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
         if (F16X3) {
-            gemm_tile<true, RB, 4>(acc, img, 128, 0, b3h, lane);
+            gemm_tile<true, 4>(acc, img, 128, 0, b3h, lane);
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) acc[rb][q] *= pow2_inv(rsz[16 * rb + 4 * g + q]) * w3_is;
         } else {
-            gemm_tile<false, RB, 8>(acc, img, 128, 0, b3, lane);
+            gemm_tile<false, 8>(acc, img, 128, 0, b3, lane);
         }
         bA.load(p.pk + kPkW1, 4, wave, 0, w1r, 0, lane);
-        if (NODE_EARLY_B) bB.load(p.pk + kPkW1, 4, 8 + wave, 0, w1r, 128, lane);
         const bool full = row0 + ROWS <= p.n;
         float *hp = p.h_out + (row0 + 4 * g) * LH + col;
 #pragma unroll
@@ -1243,10 +1112,10 @@ __global__ __launch_bounds__(512, NODE_WPE) void gnn_embed_kernel(EmbedArgs p) {
         }
     }
     __syncthreads();
-    prep<F16X3, ROWS>(stage, NLD, 0, ROWS, false, img, 128, 0, rs);
+    prep<F16X3>(stage, NLD, 0, ROWS, false, img, 128, 0, rs);
     __syncthreads();
-    proj_phase<F16X3, RB>(bA, img, rs, &rowv[0][0], w1c, p.pk, w1r, tw, row0, p.n, p.seg_n,
-                          p.a_out, p.b_out, p.rmx_out, &rng_arrived, wave, lane, NODE_EARLY_B ? &bB : nullptr);
+    proj_phase<F16X3>(bA, img, rs, &rowv[0][0], w1c, p.pk, w1r, tw, row0, p.n, p.seg_n,
+                          p.a_out, p.b_out, p.rmx_out, &rng_arrived, wave, lane);
 }
 
 inline bool al16(const void *q) { return ((uintptr_t)q & 15u) == 0; }
@@ -1261,18 +1130,12 @@ int device_cus() {
 
 }  // namespace
 
-// Node stage rows per workgroup (16 * RB)
-#ifndef MMPDE_NODE_RB
-#define MMPDE_NODE_RB 2
-#endif
-
-
 int launch_edge_stage(const float *a, const float *b, const int32_t *nbr, const int32_t *deg,
                       int64_t n, int k, int64_t seg_n, const mmpde_gnn_layer_params *p, const char *pk,
                       const float *rmx, float *mean, float *side, int64_t side_cap,
                       EdgeSplit *split, hipStream_t st, uint32_t *relu_mask, bool rng) {
     if (split) *split = EdgeSplit{};
-    MMPDE_REQUIRE(!relu_mask || (!pk && kEdgeMaskOk && al16(relu_mask)));  // the ring kernel's F32 training forward
+    MMPDE_REQUIRE(!relu_mask || (!pk && al16(relu_mask)));  // the ring kernel's F32 training forward
     MMPDE_REQUIRE(a && b && nbr && p && mean && n > 0 && k > 0 && n <= (int64_t)INT32_MAX);
     MMPDE_REQUIRE(al16(a) && al16(b) && al16(p->msg2_w) && al16(mean));
     MMPDE_REQUIRE(!pk || (rmx && al16(pk) && al16(rmx)));
@@ -1285,11 +1148,10 @@ int launch_edge_stage(const float *a, const float *b, const int32_t *nbr, const 
         return launch_edge_wave(a, b, nbr, deg, n, k, seg_n, p->msg2_b, pk, rmx, rng, mean, side, side_cap, cus,
                                 split, st);
     // F32: the exact fp32 ring kernel
-    EdgeArgs e{a, b, nbr, n, k, (int)ntiles, p->msg2_w, p->msg2_b, nullptr, nullptr, mean, nullptr, deg, relu_mask};
+    EdgeArgs e{a, b, nbr, n, k, (int)ntiles, p->msg2_w, p->msg2_b, nullptr, nullptr, mean, deg, relu_mask};
     const int grid = ntiles < cus ? (int)ntiles : cus;
-    const dim3 block(64 * (4 * EDGE_NC + 4 * EDGE_NP));
-    if (deg) hipLaunchKernelGGL((gnn_edge_kernel<false, EDGE_PH, EDGE_NC, EDGE_NP, true>), dim3(grid), block, 0, st, e);
-    else hipLaunchKernelGGL(gnn_edge_kernel<false>, dim3(grid), block, 0, st, e);
+    if (deg) hipLaunchKernelGGL((gnn_edge_kernel<false, true>), dim3(grid), dim3(768), 0, st, e);
+    else hipLaunchKernelGGL((gnn_edge_kernel<false, false>), dim3(grid), dim3(768), 0, st, e);
     MMPDE_RET_LAUNCH();
     return MMPDE_OK;
 }
@@ -1338,19 +1200,16 @@ __global__ __launch_bounds__(256) void edge_finish_kernel(float *__restrict__ me
     float4 x[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) x[q] = *(const float4 *)(mp + 4 * q);
-    const int64_t S = sp.S, G = sp.units, kk = sp.k;
-    const int64_t sg = row / sp.seg_n, ql = row - sg * sp.seg_n, t = ql / 16;
-    const int64_t lo = max(((t * kk + 1) * G + S - 1) / S, (int64_t)1);
-    const int64_t hi = min(((t + 1) * kk * G + S - 1) / S - 1, G - 1);
-    for (int64_t w = lo; w <= hi; ++w) {
-        const float *q4 = sp.side + ((sg * G + w) * 16 + (ql & 15)) * LH + 16 * part;
+    const SideUnits su = side_units(sp, row);
+    for (int64_t w = su.lo; w <= su.hi; ++w) {
+        const float *q4 = sp.side + ((su.sg * sp.units + w) * 16 + (su.q & 15)) * LH + 16 * part;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float4 y = *(const float4 *)(q4 + 4 * q);
             x[q] = make_float4(x[q].x + y.x, x[q].y + y.y, x[q].z + y.z, x[q].w + y.w);
         }
     }
-    div_rows_rn(x, deg ? (float)max(deg[row], 1) : (float)kk);
+    div_rows_rn(x, deg ? (float)max(deg[row], 1) : (float)sp.k);
 #pragma unroll
     for (int q = 0; q < 4; ++q) *(float4 *)(mp + 4 * q) = x[q];
 }
@@ -1373,7 +1232,7 @@ int launch_edge_mean_f16x3(const float *a, const float *b, const int32_t *nbr, c
                            hipStream_t st) {
     MMPDE_REQUIRE(a && b && nbr && w2 && b2 && mean && ws && n > 0 && k > 0 && n <= (int64_t)INT32_MAX);
     MMPDE_REQUIRE(al16(a) && al16(b) && al16(w2) && al16(mean) && al16(ws));
-    MMPDE_REQUIRE(!relu_mask || (kEdgeMaskOk && al16(relu_mask)));
+    MMPDE_REQUIRE(!relu_mask || al16(relu_mask));
     const int64_t ntiles = (n + ET - 1) / ET;
     MMPDE_REQUIRE(ntiles * ((k + ESL - 1) / ESL) < (int64_t)INT32_MAX);
     char *pk = (char *)ws;
@@ -1402,58 +1261,10 @@ int launch_edge_mean_f16x3(const float *a, const float *b, const int32_t *nbr, c
     hipLaunchKernelGGL(row_scale_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, rmx, nbr, deg, n, k,
                        rsc);
     MMPDE_RET_LAUNCH();
-    EdgeArgs e{a, b, nbr, n, k, (int)ntiles, w2, b2, pk, rsc, mean, nullptr, deg, relu_mask};
+    EdgeArgs e{a, b, nbr, n, k, (int)ntiles, w2, b2, pk, rsc, mean, deg, relu_mask};
     const int grid = ntiles < cus ? (int)ntiles : cus;
-    const dim3 block(64 * (4 * EDGE_NC + 4 * EDGE_NP));
-    if (deg) hipLaunchKernelGGL((gnn_edge_kernel<true, EDGE_PH, EDGE_NC, EDGE_NP, true>), dim3(grid), block, 0, st, e);
-    else hipLaunchKernelGGL(gnn_edge_kernel<true>, dim3(grid), block, 0, st, e);
-    MMPDE_RET_LAUNCH();
-    return MMPDE_OK;
-}
-
-// The kernel arguments of one node-stage call (validated).
-static int node_args(const NodeStageCall &c, NodeArgs *out) {
-    const bool sums = c.split && c.split->units > 0;
-    MMPDE_REQUIRE(!sums || (c.split->side && c.split->S > 0 && c.split->k > 0 && c.split->seg_n > 0 &&
-                            c.n % c.split->seg_n == 0));
-    MMPDE_REQUIRE(!c.rmx_out || al16(c.rmx_out));
-    MMPDE_REQUIRE(c.h && c.mean && c.u && c.pos && c.p && c.h_out && c.n > 0);
-    MMPDE_REQUIRE(al16(c.h) && al16(c.mean) && al16(c.h_out));
-    MMPDE_REQUIRE(c.p->upd1_ld >= 257 && (c.p->upd1_ld & 3) == 0 && al16(c.p->upd1_w) && al16(c.p->upd2_w));
-    MMPDE_REQUIRE(!c.pk || (al16(c.pk) && (!c.next || c.pkn)));
-    const mmpde_gnn_layer_params *p = c.p;
-    NodeArgs a{c.h, c.mean, c.n, p->upd1_w, p->upd1_b, p->upd1_ld, p->upd2_w, p->upd2_b, p->bn_w, p->bn_b,
-               p->bn_rm, p->bn_rv, p->eps, c.h_out, nullptr, nullptr, 0, c.a_out, c.b_out, c.u, c.pos, c.sc,
-               c.pk, c.pkn, c.rmx_out, effective_seg(c.n, c.seg_n), 1, 0, sums ? c.deg : nullptr,
-               sums ? c.split->k : 0};
-    if (sums) a.split = *c.split;
-    if (c.next) {
-        MMPDE_REQUIRE(c.a_out && c.b_out && c.next->msg1_ld >= 260 && (c.next->msg1_ld & 3) == 0 &&
-                      al16(c.next->msg1_w));
-        a.w1n = c.next->msg1_w;
-        a.b1n = c.next->msg1_b;
-        a.ld_w1n = c.next->msg1_ld;
-    }
-    *out = a;
-    return MMPDE_OK;
-}
-
-static int launch_node_stage(const NodeStageCall &c, hipStream_t st) {
-    constexpr int RB = MMPDE_NODE_RB;
-    NodeArgs a;
-    int rc = node_args(c, &a);
-    if (rc) return rc;
-    const bool next = c.next != nullptr, f16 = c.pk != nullptr;
-    const int64_t tiles = ceil_div(c.n, 16 * RB);
-    MMPDE_REQUIRE(tiles < (int64_t)INT32_MAX);
-    const dim3 grid((unsigned)tiles);
-#define MMPDE_NODE(NX, SPLIT) \
-    hipLaunchKernelGGL((gnn_node_kernel<NX, SPLIT, RB>), grid, dim3(512), 0, st, a)
-    if (next && f16) MMPDE_NODE(true, true);
-    else if (next) MMPDE_NODE(true, false);
-    else if (f16) MMPDE_NODE(false, true);
-    else MMPDE_NODE(false, false);
-#undef MMPDE_NODE
+    if (deg) hipLaunchKernelGGL((gnn_edge_kernel<true, true>), dim3(grid), dim3(768), 0, st, e);
+    else hipLaunchKernelGGL((gnn_edge_kernel<true, false>), dim3(grid), dim3(768), 0, st, e);
     MMPDE_RET_LAUNCH();
     return MMPDE_OK;
 }
@@ -1463,31 +1274,36 @@ int launch_node_stage(const float *h, const float *mean, const EdgeSplit *split,
                       const mmpde_gnn_layer_params *p, const mmpde_gnn_layer_params *next,
                       const char *pk, const char *pkn, float *rmx_out, float *h_out, float *a_out,
                       float *b_out, hipStream_t st) {
-    const NodeStageCall c{h, mean, split, deg, u, pos, n, seg_n, sc, p, next, pk, pkn, rmx_out, h_out, a_out,
-                          b_out};
-    return launch_node_stage(c, st);
-}
-
-static int embed_args(const EmbedStageCall &c, EmbedArgs *out) {
-    MMPDE_REQUIRE(c.u && c.pos && c.e && c.l0 && c.h_out && c.a_out && c.b_out && c.n > 0);
-    MMPDE_REQUIRE(al16(c.e->w3) && al16(c.h_out) && al16(c.a_out) && al16(c.b_out));
-    MMPDE_REQUIRE(c.l0->msg1_ld >= 260 && (c.l0->msg1_ld & 3) == 0 && al16(c.l0->msg1_w));
-    MMPDE_REQUIRE(!c.pk0 || (al16(c.pk0) && c.rmx_out && al16(c.rmx_out)));
-    *out = EmbedArgs{c.u, c.pos, c.n, c.sc, *c.e, c.h_out, c.l0->msg1_w, c.l0->msg1_b, c.l0->msg1_ld, c.a_out,
-                     c.b_out, c.pk0, c.rmx_out, effective_seg(c.n, c.seg_n)};
-    return MMPDE_OK;
-}
-
-static int launch_embed_stage(const EmbedStageCall &c, hipStream_t st) {
-    constexpr int RB = MMPDE_NODE_RB;
-    EmbedArgs a;
-    int rc = embed_args(c, &a);
-    if (rc) return rc;
-    const int64_t tiles = ceil_div(c.n, 16 * RB);
+    const bool sums = split && split->units > 0;
+    MMPDE_REQUIRE(!sums || (split->side && split->S > 0 && split->k > 0 && split->seg_n > 0 &&
+                            n % split->seg_n == 0));
+    MMPDE_REQUIRE(!rmx_out || al16(rmx_out));
+    MMPDE_REQUIRE(h && mean && u && pos && p && h_out && n > 0);
+    MMPDE_REQUIRE(al16(h) && al16(mean) && al16(h_out));
+    MMPDE_REQUIRE(p->upd1_ld >= 257 && (p->upd1_ld & 3) == 0 && al16(p->upd1_w) && al16(p->upd2_w));
+    MMPDE_REQUIRE(!pk || (al16(pk) && (!next || pkn)));
+    NodeArgs a{h, mean, n, p->upd1_w, p->upd1_b, p->upd1_ld, p->upd2_w, p->upd2_b, p->bn_w, p->bn_b,
+               p->bn_rm, p->bn_rv, p->eps, h_out, nullptr, nullptr, 0, a_out, b_out, u, pos, sc,
+               pk, pkn, rmx_out, effective_seg(n, seg_n), sums ? deg : nullptr,
+               sums ? split->k : 0};
+    if (sums) a.split = *split;
+    if (next) {
+        MMPDE_REQUIRE(a_out && b_out && next->msg1_ld >= 260 && (next->msg1_ld & 3) == 0 &&
+                      al16(next->msg1_w));
+        a.w1n = next->msg1_w;
+        a.b1n = next->msg1_b;
+        a.ld_w1n = next->msg1_ld;
+    }
+    const int64_t tiles = ceil_div(n, ROWS);
     MMPDE_REQUIRE(tiles < (int64_t)INT32_MAX);
     const dim3 grid((unsigned)tiles);
-    if (c.pk0) hipLaunchKernelGGL((gnn_embed_kernel<true, RB>), grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((gnn_embed_kernel<false, RB>), grid, dim3(512), 0, st, a);
+    const bool f16 = pk != nullptr;
+#define MMPDE_NODE(NX, F16) hipLaunchKernelGGL((gnn_node_kernel<NX, F16>), grid, dim3(512), 0, st, a)
+    if (next && f16) MMPDE_NODE(true, true);
+    else if (next) MMPDE_NODE(true, false);
+    else if (f16) MMPDE_NODE(false, true);
+    else MMPDE_NODE(false, false);
+#undef MMPDE_NODE
     MMPDE_RET_LAUNCH();
     return MMPDE_OK;
 }
@@ -1496,6 +1312,17 @@ int launch_embed_stage(const float *u, const float *pos, int64_t n, int64_t seg_
                        const mmpde_gnn_embed_params *e, const mmpde_gnn_layer_params *l0,
                        const char *pk0, float *rmx_out, float *h_out, float *a_out,
                        float *b_out, hipStream_t st) {
-    const EmbedStageCall c{u, pos, n, seg_n, sc, e, l0, pk0, rmx_out, h_out, a_out, b_out};
-    return launch_embed_stage(c, st);
+    MMPDE_REQUIRE(u && pos && e && l0 && h_out && a_out && b_out && n > 0);
+    MMPDE_REQUIRE(al16(e->w3) && al16(h_out) && al16(a_out) && al16(b_out));
+    MMPDE_REQUIRE(l0->msg1_ld >= 260 && (l0->msg1_ld & 3) == 0 && al16(l0->msg1_w));
+    MMPDE_REQUIRE(!pk0 || (al16(pk0) && rmx_out && al16(rmx_out)));
+    const EmbedArgs a{u, pos, n, sc, *e, h_out, l0->msg1_w, l0->msg1_b, l0->msg1_ld, a_out,
+                      b_out, pk0, rmx_out, effective_seg(n, seg_n)};
+    const int64_t tiles = ceil_div(n, ROWS);
+    MMPDE_REQUIRE(tiles < (int64_t)INT32_MAX);
+    const dim3 grid((unsigned)tiles);
+    if (pk0) hipLaunchKernelGGL(gnn_embed_kernel<true>, grid, dim3(512), 0, st, a);
+    else hipLaunchKernelGGL(gnn_embed_kernel<false>, grid, dim3(512), 0, st, a);
+    MMPDE_RET_LAUNCH();
+    return MMPDE_OK;
 }

@@ -95,6 +95,29 @@ struct EdgeSplit {
     int64_t seg_n = 0;     // rows per segment
 };
 
+// The side blocks of global row `row` (segment sg, local row q, tile t = q / 16):
+// side[sg * U + u][q % 16] for u = lo .. hi (none when lo > hi), the units
+// whose first slot s0(u) = floor(u S / U) lies strictly inside the row's tile,
+// t k < s0(u) < (t + 1) k.  tests/test_slot_split.py restates this closed form
+// and checks it against the kernel's slot stream.  Needs sp.units > 0.
+struct SideUnits {
+    int64_t sg, q, lo, hi;
+};
+__device__ __forceinline__ SideUnits side_units(const EdgeSplit &sp, int64_t row) {
+    const int64_t S = sp.S, U = sp.units, k = sp.k;
+    if ((uint64_t)(S + 1) * (uint64_t)(U + 1) + (uint64_t)sp.seg_n < 0xffffffffull) {
+        // 32-bit divisions (wave-uniform test: a 64-bit one is a long
+        // instruction sequence, three per row here)
+        const uint32_t sn = (uint32_t)sp.seg_n, r32 = (uint32_t)row;
+        const uint32_t sg = r32 / sn, q = r32 - sg * sn, t = q / 16;
+        const uint32_t S32 = (uint32_t)S, U32 = (uint32_t)U, k32 = (uint32_t)k;
+        return {sg, q, max(((t * k32 + 1) * U32 + S32 - 1) / S32, 1u),
+                min(((t + 1) * k32 * U32 + S32 - 1) / S32 - 1, U32 - 1)};
+    }
+    const int64_t sg = row / sp.seg_n, q = row - sg * sp.seg_n, t = q / 16;
+    return {sg, q, max(((t * k + 1) * U + S - 1) / S, (int64_t)1), min(((t + 1) * k * U + S - 1) / S - 1, U - 1)};
+}
+
 // Edge stage: mean[i] = (1/k) sum_e relu(W2 relu(a_i + b_nbr(i,e)) + b2)
 // (message_net_2 + PyG mean aggregation); with deg != nullptr the sum runs
 // over e < deg[i] and divides by max(deg[i], 1).  F16X3: pk = this layer's
@@ -160,19 +183,6 @@ int launch_node_stage(const float *h, const float *mean, const EdgeSplit *split,
                       const char *pk, const char *pkn, float *rmx_out, float *h_out, float *a_out,
                       float *b_out, hipStream_t st);
 
-// The arguments of one launch_node_stage call.
-struct NodeStageCall {
-    const float *h, *mean;
-    const EdgeSplit *split;
-    const int32_t *deg;
-    const float *u, *pos;
-    int64_t n, seg_n;
-    mmpde_gnn_scales sc;
-    const mmpde_gnn_layer_params *p, *next;
-    const char *pk, *pkn;
-    float *rmx_out, *h_out, *a_out, *b_out;
-};
-
 // Embedding (gnn_2d.py:99-106) + layer 0's message_net_1 node halves in one
 // launch: h_out = embedding_mlp(cat(u, x/Lx, y/Ly, t/tmax)), a_out / b_out as
 // launch_node_stage's.  F16X3 projection when pk0 (layer 0's images) != nullptr.
@@ -180,14 +190,3 @@ int launch_embed_stage(const float *u, const float *pos, int64_t n, int64_t seg_
                        const mmpde_gnn_embed_params *e, const mmpde_gnn_layer_params *l0,
                        const char *pk0, float *rmx_out, float *h_out, float *a_out,
                        float *b_out, hipStream_t st);
-
-// launch_embed_stage's arguments.
-struct EmbedStageCall {
-    const float *u, *pos;
-    int64_t n, seg_n;
-    mmpde_gnn_scales sc;
-    const mmpde_gnn_embed_params *e;
-    const mmpde_gnn_layer_params *l0;
-    const char *pk0;
-    float *rmx_out, *h_out, *a_out, *b_out;
-};
