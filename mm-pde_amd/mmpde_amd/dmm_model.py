@@ -183,22 +183,7 @@ class DMM(nn.Module):
             raise ValueError("grid rows must be a multiple of the batch size")
         lib = L.lib()
         st = L.stream(u.device)
-        branch = torch.empty((B, hd.latent), dtype=torch.float32, device=u.device)
-        if self.mode == "graph":
-            og = L.f32c(torch.as_tensor(self.ori_grid).to(u.device)).reshape(-1, 2)
-            N = og.shape[0]
-            nbr = self.grid_nbr(og)
-            ws = torch.empty((lib.mmpde_dmm_workspace_bytes(B, N, hd.latent, hd.hidden) // 4,),
-                             dtype=torch.float32, device=u.device)
-            L.check(lib.mmpde_dmm_branch_graph(L.ptr(u), L.ptr(og), B, N, L.ptr(nbr), nbr.shape[1],
-                                               ctypes.byref(bp), ctypes.byref(hd), L.ptr(ws),
-                                               L.ptr(branch), st), "mmpde_dmm_branch_graph")
-        else:
-            s = self.branch.s
-            ws = torch.empty((lib.mmpde_dmm_workspace_bytes(B, s * s, hd.latent, hd.hidden) // 4,),
-                             dtype=torch.float32, device=u.device)
-            L.check(lib.mmpde_dmm_branch_array(L.ptr(u), B, ctypes.byref(bp), ctypes.byref(hd),
-                                               L.ptr(ws), L.ptr(branch), st), "mmpde_dmm_branch_array")
+        branch = self.branch_features(u)
         nb = lib.mmpde_dmm_phi_workspace_bytes(B, ng, hd.latent, hd.hidden, hd.th)
         ws2 = torch.empty((nb // 4,), dtype=torch.float32, device=u.device)
         phi = torch.empty((ng, 1), dtype=torch.float32, device=u.device)
@@ -324,6 +309,58 @@ class DMM(nn.Module):
         return hit[1]
 
     # ----------------------------------------------------------------- the API
+    @staticmethod
+    def _local_nbr(nbr: torch.Tensor, n: int, device) -> torch.Tensor:
+        """A caller's [N, k] int32 LOCAL neighbour table, checked for the kernels."""
+        L.require_device(nbr)
+        if nbr.dtype != torch.int32 or nbr.dim() != 2 or nbr.shape[0] != n or nbr.device != device:
+            raise ValueError("nbr must be an [N, k] int32 table of local indices on u's device")
+        return nbr.contiguous()
+
+    @staticmethod
+    def _workspace(workspace, B, n, hd, device) -> torch.Tensor:
+        """The caller's workspace, checked against mmpde_dmm_workspace_bytes, or a new one."""
+        nb = L.lib().mmpde_dmm_workspace_bytes(B, n, hd.latent, hd.hidden)
+        if workspace is None:
+            return torch.empty((nb // 4,), dtype=torch.float32, device=device)
+        L.require_device(workspace)
+        if workspace.numel() * workspace.element_size() < nb:
+            raise ValueError("workspace is smaller than mmpde_dmm_workspace_bytes")
+        return workspace
+
+    def branch_features(self, u: torch.Tensor, nbr: torch.Tensor | None = None,
+                        workspace: torch.Tensor | None = None) -> torch.Tensor:
+        """The branch of forward (dmm_model.py:188,197-210) alone.
+        u: graph mode [B, N] (values on self.ori_grid), array mode [B, s, s];
+        nbr: graph mode only, an [N, k] int32 local neighbour table of any k used
+        instead of the kNN-35 table of self.ori_grid.  Returns [B, L] fp32."""
+        L.require_device(u)
+        if self.training:
+            raise NotImplementedError("branch_features is eval-mode: call .eval()")
+        bp, hd = self.device_params()
+        u = L.f32c(u)
+        B = u.shape[0]
+        lib = L.lib()
+        st = L.stream(u.device)
+        branch = torch.empty((B, hd.latent), dtype=torch.float32, device=u.device)
+        if self.mode == "graph":
+            og = L.f32c(torch.as_tensor(self.ori_grid).to(u.device)).reshape(-1, 2)
+            N = og.shape[0]
+            nbr = self.grid_nbr(og) if nbr is None else self._local_nbr(nbr, N, u.device)
+            workspace = self._workspace(workspace, B, N, hd, u.device)
+            L.check(lib.mmpde_dmm_branch_graph(L.ptr(u), L.ptr(og), B, N, L.ptr(nbr), nbr.shape[1],
+                                               ctypes.byref(bp), ctypes.byref(hd), L.ptr(workspace),
+                                               L.ptr(branch), st), "mmpde_dmm_branch_graph")
+        else:
+            if nbr is not None:
+                raise ValueError("nbr is a graph-mode argument")
+            s = self.branch.s
+            workspace = self._workspace(workspace, B, s * s, hd, u.device)
+            L.check(lib.mmpde_dmm_branch_array(L.ptr(u), B, ctypes.byref(bp), ctypes.byref(hd),
+                                               L.ptr(workspace), L.ptr(branch), st),
+                    "mmpde_dmm_branch_array")
+        return branch
+
     def head_cache(self, xi: torch.Tensor, workspace: torch.Tensor | None = None) -> torch.Tensor:
         """The grid side of the head (trunk(xi), Q, J = dQ/dxi): a function of xi
         and the weights only, prepared once for a rollout over a fixed grid and
@@ -344,12 +381,15 @@ class DMM(nn.Module):
 
     def mesh(self, u: torch.Tensor, xi: torch.Tensor, out: torch.Tensor | None = None,
              workspace: torch.Tensor | None = None,
-             head_cache: torch.Tensor | None = None) -> torch.Tensor:
+             head_cache: torch.Tensor | None = None,
+             nbr: torch.Tensor | None = None) -> torch.Tensor:
         """Moved mesh x = xi + d(phi)/d(xi) for every trajectory.
         u: graph mode [B, N] (values on the fixed grid), array mode [B, s, s];
         xi: [N, 2] grid shared by all trajectories (graph: self.ori_grid;
         array: the np.meshgrid 'xy' grid of data_creator_2d.py:94-100);
-        head_cache: head_cache(xi) of the same xi and weights, or None.
+        head_cache: head_cache(xi) of the same xi and weights, or None;
+        nbr: graph mode only, an [N, k] int32 local neighbour table of any k used
+        instead of the kNN-35 table of xi.
         Returns [B*N, 2] fp32."""
         L.require_device(u, xi)
         bp, hd = self.device_params()
@@ -369,11 +409,13 @@ class DMM(nn.Module):
         hc = L.ptr(head_cache) if head_cache is not None else None
         st = L.stream(u.device)
         if self.mode == "graph":
-            nbr = self.grid_nbr(xi)
+            nbr = self.grid_nbr(xi) if nbr is None else self._local_nbr(nbr, N, u.device)
             L.check(L.lib().mmpde_dmm_mesh_graph_cached(
                 L.ptr(u), L.ptr(xi), B, N, L.ptr(nbr), nbr.shape[1], ctypes.byref(bp),
                 ctypes.byref(hd), hc, L.ptr(workspace), L.ptr(out), st), "mmpde_dmm_mesh_graph")
         else:
+            if nbr is not None:
+                raise ValueError("nbr is a graph-mode argument")
             L.check(L.lib().mmpde_dmm_mesh_array_cached(
                 L.ptr(u), L.ptr(xi), B, N, ctypes.byref(bp), ctypes.byref(hd), hc,
                 L.ptr(workspace), L.ptr(out), st), "mmpde_dmm_mesh_array")

@@ -313,38 +313,42 @@ def dmm_gnn_layer(sd, p, x, u, pos_x, pos_y, edge_index, train=False):
     return _bn(sd, p + ".norm.module", x + upd, train=train)
 
 
+def dmm_branch(sd, mode, u, ori_grid=None, hidden_layer=3, grid_edge_index=None, train=False):
+    """The branch of DMM.forward, dmm_model.py:197-210 (graph) / :188 (array):
+    u [B, N] on `ori_grid` (graph) or [B, s, s] (array) -> [B, L], in the dtype
+    of its inputs."""
+    B = u.shape[0]
+    if mode == "array":
+        return convnet(sd, "branch", u.unsqueeze(1))
+    # create_graph, dmm_model.py:222-234 (kNN-35 on the fixed grid)
+    gpos = ori_grid[None].repeat(B, 1, 1).reshape(-1, 2)
+    if grid_edge_index is None:
+        grid_edge_index, _, _ = knn_graph(gpos, 35, B)
+    x = u.reshape(-1, 1)
+    pos_x = gpos[:, 0][:, None]
+    pos_y = gpos[:, 1][:, None]
+    h = _lin(sd, "embedding_mlp.0", torch.cat((x, pos_x, pos_y), -1))
+    h = torch.tanh(_bn(sd, "embedding_mlp.1", h, train=train))
+    h = _bn(sd, "embedding_mlp.4", _lin(sd, "embedding_mlp.3", h), train=train)
+    for i in range(hidden_layer):
+        h = dmm_gnn_layer(sd, f"gnn_layers.{i}", h, x, pos_x, pos_y, grid_edge_index,
+                          train=train)
+    h, _ = densenet(sd, "decoding_mlp", h, 2)
+    b = h.reshape(B, 1, -1)
+    b = torch.tanh(_lin(sd, "output_mlp.0", b))
+    b = torch.tanh(_lin(sd, "output_mlp.2", b))
+    return _lin(sd, "output_mlp.4", b).reshape(B, -1)
+
+
 def dmm_forward(sd, mode, u, grid, ori_grid=None, hidden_layer=3, grid_edge_index=None,
                 train=False):
     """DMM.forward(u, grid), dmm_model.py:185-219.  `grid` is xi [B*N, 2].
     train=True: the train() forward of DMM training (BatchNorm on batch
     statistics, running buffers of `sd` updated)."""
-    B = u.shape[0]
-    if mode == "array":
-        branch = convnet(sd, "branch", u.unsqueeze(1)).unsqueeze(1)
-        branch = branch.repeat(1, int(grid.shape[0] / u.shape[0]), 1)
-        trunk, _ = densenet(sd, "trunk", grid, 2)
-    else:
-        # create_graph, dmm_model.py:222-234 (kNN-35 on the fixed grid)
-        N = ori_grid.shape[0]
-        gpos = ori_grid[None].repeat(B, 1, 1).reshape(-1, 2)
-        if grid_edge_index is None:
-            grid_edge_index, _, _ = knn_graph(gpos, 35, B)
-        x = u.reshape(-1, 1)
-        pos_x = gpos[:, 0][:, None]
-        pos_y = gpos[:, 1][:, None]
-        h = _lin(sd, "embedding_mlp.0", torch.cat((x, pos_x, pos_y), -1))
-        h = torch.tanh(_bn(sd, "embedding_mlp.1", h, train=train))
-        h = _bn(sd, "embedding_mlp.4", _lin(sd, "embedding_mlp.3", h), train=train)
-        for i in range(hidden_layer):
-            h = dmm_gnn_layer(sd, f"gnn_layers.{i}", h, x, pos_x, pos_y, grid_edge_index,
-                              train=train)
-        h, _ = densenet(sd, "decoding_mlp", h, 2)
-        b = h.reshape(B, 1, -1)
-        b = torch.tanh(_lin(sd, "output_mlp.0", b))
-        b = torch.tanh(_lin(sd, "output_mlp.2", b))
-        b = _lin(sd, "output_mlp.4", b)
-        branch = b.repeat(1, int(grid.shape[0] / u.shape[0]), 1)
-        trunk, _ = densenet(sd, "trunk", grid, 2)
+    branch = dmm_branch(sd, mode, u, ori_grid=ori_grid, hidden_layer=hidden_layer,
+                        grid_edge_index=grid_edge_index, train=train).unsqueeze(1)
+    branch = branch.repeat(1, int(grid.shape[0] / u.shape[0]), 1)
+    trunk, _ = densenet(sd, "trunk", grid, 2)
     out, _ = densenet(sd, "out_nn",
                       torch.cat((branch.reshape(-1, branch.shape[-1]),
                                  trunk.reshape(-1, branch.shape[-1])), dim=-1), 2)
@@ -404,16 +408,17 @@ def interpolate(itp_sd, u, init_x, init_y, x, y, mode, burgers=False, return_idx
     return out
 
 
-def moving_mesh_tri(dmm_sd, u, grid_x, grid_y, ori_grid, grid_edge_index=None):
-    """data_creator_2d.py:115-137 -- x = xi + d(phi)/d(xi) via two autograd.grad."""
+def moving_mesh_tri(dmm_sd, u, grid_x, grid_y, ori_grid, grid_edge_index=None, hidden_layer=3):
+    """data_creator_2d.py:115-137 -- x = xi + d(phi)/d(xi) via two autograd.grad
+    (in the dtype of its inputs)."""
     xi1, xi2 = grid_x.reshape(-1, 1).clone(), grid_y.reshape(-1, 1).clone()
     xi1.requires_grad = True
     xi2.requires_grad = True
     with torch.enable_grad():
         xi = torch.cat((xi1, xi2), dim=-1)
-        phi = dmm_forward(dmm_sd, "graph", u, xi, ori_grid=ori_grid,
+        phi = dmm_forward(dmm_sd, "graph", u, xi, ori_grid=ori_grid, hidden_layer=hidden_layer,
                           grid_edge_index=grid_edge_index)
-        w = torch.ones(phi.shape)
+        w = torch.ones_like(phi)
         x1 = torch.autograd.grad(phi, xi1, grad_outputs=w, retain_graph=True,
                                  create_graph=True, allow_unused=True)[0] + xi1
         x2 = torch.autograd.grad(phi, xi2, grad_outputs=w, retain_graph=True,
