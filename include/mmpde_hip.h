@@ -622,6 +622,11 @@ typedef struct {
                                 scale per segment, so a trajectory's output does not
                                 depend on the others in the launch.  0 (or a value
                                 that does not divide n, or < 32): one segment */
+    float *h_last;           /* output, or NULL: [n, 128] (16-byte aligned), the last layer's
+                                node features h'.  The last layer's node kernel runs the
+                                output head on its rows itself and otherwise does not store
+                                them; mmpde_gnn_head on h_last reproduces `out` bit for bit.
+                                Ignored with n_layers == 0 */
 } mmpde_gnn_exec;
 
 /* Most layers mmpde_gnn_forward_ex accepts (sizes the workspace's packed

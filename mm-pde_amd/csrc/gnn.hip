@@ -353,6 +353,11 @@ __global__ __launch_bounds__(256) void head_kernel(HeadArgs2 hp) {
 
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
+// Rows the forward workspace's [n, H] buffers are sized for: at least 6, so
+// that the three buffers after the mean hold one 16-row side block (the wave
+// edge kernel needs one per segment) however small n is.
+inline int64_t ws_rows(int64_t n) { return n < 6 ? 6 : n; }
+
 }  // namespace
 
 // ===========================================================================
@@ -363,7 +368,7 @@ extern "C" int64_t mmpde_gnn_workspace_bytes(int64_t n) {
     // kernel's side blocks = 8 x [n,128] fp32 (the unfused per-layer API uses 4
     // of them as a, b, mean, v), then the F16X3 row maxima (layer.hpp) and
     // room for per-call weight images
-    return kGnnBufs * n * H * (int64_t)sizeof(float) + row_records_floats(n) * 4 +
+    return kGnnBufs * ws_rows(n) * H * (int64_t)sizeof(float) + row_records_floats(n) * 4 +
            (int64_t)MMPDE_GNN_MAX_LAYERS * kLayerPack;
 }
 
@@ -564,13 +569,14 @@ extern "C" int mmpde_gnn_forward_ex(const float *u, const float *pos, int64_t n,
     MMPDE_REQUIRE(mode == MMPDE_EDGE_GEMM_F32 || mode == MMPDE_EDGE_GEMM_F16X3);
     hipStream_t st = as_stream(stream);
     float *ws = (float *)workspace;
-    float *hb[2] = {ws, ws + n * H};
-    float *wa = ws + 2 * n * H, *wb = ws + 3 * n * H, *wmean = ws + 4 * n * H;
+    const int64_t nr = ws_rows(n);  // buffer stride (rows)
+    float *hb[2] = {ws, ws + nr * H};
+    float *wa = ws + 2 * nr * H, *wb = ws + 3 * nr * H, *wmean = ws + 4 * nr * H;
     const char *pack = nullptr;
     // row maxima and range records of the current layer's message inputs
     // (F16X3 split scales):
     // written by the embed / node stage, read by the next edge stage
-    float *rmx = ws + kGnnBufs * n * H;
+    float *rmx = ws + kGnnBufs * nr * H;
     // rows per trajectory segment (the edge stage's summation units)
     const int64_t seg_n = exec ? exec->seg_n : 0;
     int rc;
@@ -579,7 +585,7 @@ extern "C" int mmpde_gnn_forward_ex(const float *u, const float *pos, int64_t n,
             MMPDE_REQUIRE(aligned16(exec->packed));
             pack = (const char *)exec->packed;
         } else {
-            char *wpk = (char *)(ws + kGnnBufs * n * H + row_records_floats(n));
+            char *wpk = (char *)(ws + kGnnBufs * nr * H + row_records_floats(n));
             rc = mmpde_gnn_pack_f16x3(layers, n_layers, wpk, stream);
             if (rc) return rc;
             pack = wpk;
@@ -610,17 +616,21 @@ extern "C" int mmpde_gnn_forward_ex(const float *u, const float *pos, int64_t n,
         const int32_t *deg = exec ? exec->degree : nullptr;
         // side blocks of the wave edge kernel: the workspace after the mean
         rc = launch_edge_stage(wa, wb, nbr, deg, n, k, seg_n, &layers[l], pk, pack ? rmx : nullptr, wmean,
-                               wmean + n * H, (kGnnBufs - 5) * n * H / (16 * H), &split, st);
+                               wmean + nr * H, (kGnnBufs - 5) * nr * H / (16 * H), &split, st);
         if (rc) return rc;
         if (ee && hipEventRecord(ee, st) != hipSuccess) return MMPDE_ERR_INVALID_ARG;
-        // a, b are rewritten in place: this layer's edge stage has consumed them
+        // a, b are rewritten in place: this layer's edge stage has consumed them.
+        // The last layer's node kernel runs the output head on its rows of h'
+        // itself and stores h' only into exec->h_last, when the caller asks
         rc = launch_node_stage(hb[cur], wmean, &split, deg, u, pos, n, seg_n, sc, &layers[l], next, pk, pkn,
-                               rout, hb[cur ^ 1], wa, wb, st);
+                               rout, next ? hb[cur ^ 1] : (exec ? exec->h_last : nullptr), wa, wb, st,
+                               next ? nullptr : head, next ? nullptr : out);
         if (rc) return rc;
         if (ne && hipEventRecord(ne, st) != hipSuccess) return MMPDE_ERR_INVALID_ARG;
         cur ^= 1;
     }
-    return mmpde_gnn_head(hb[cur], n, head, out, stream);
+    if (n_layers > 0) return MMPDE_OK;
+    return mmpde_gnn_head(hb[cur], n, head, out, stream);  // no layer: the embedding's rows
 }
 
 extern "C" int mmpde_gnn_forward(const float *u, const float *pos, int64_t n, int k,

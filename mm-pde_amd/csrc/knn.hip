@@ -164,6 +164,18 @@ __device__ __forceinline__ K shfl_xor_key(K v, int m, int lane) {
     }
 }
 
+// Maximum / minimum of v over the wave's 64 lanes (all active), on every lane.
+__device__ __forceinline__ uint32_t wave_umax(uint32_t v, int lane) {
+#pragma unroll
+    for (int j = 1; j <= 32; j <<= 1) v = max(v, xor_lane(v, j, lane));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_umin(uint32_t v, int lane) {
+#pragma unroll
+    for (int j = 1; j <= 32; j <<= 1) v = min(v, xor_lane(v, j, lane));
+    return v;
+}
+
 // Bitonic sort of one key per lane across the wave, ascending in lane order.
 template <typename K>
 __device__ __forceinline__ K wave_sort64(K v, int lane) {
@@ -825,9 +837,11 @@ __device__ __forceinline__ float cand_bound_cells(float rq, float2 q, const floa
     return -wave_max(-L);
 }
 
-// One wave per query point: the 128 candidates' keys (two per lane), one
-// 128-wide (key, index) sort; the first kk are the answer when the kk-th
-// candidate is closer than the bound.  QUERY = false: the moved-mesh graph
+// One wave per query point: the 128 candidates' keys (two per lane), those that
+// can be among the first kk selected and sorted by (key, index) -- 64 wide in
+// one register when at most 64 remain, else the 128-wide sort of all; the
+// first kk are the answer when the kk-th candidate is closer than the bound.
+// QUERY = false: the moved-mesh graph
 // (fp32 keys, self dropped, global indices, as knn_finish's graph branch; ref =
 // xi); true: the kNN query of qry onto the moved mesh (fp64 keys, local
 // indices; ref = the fixed query points the table was built for).
@@ -890,6 +904,48 @@ __global__ __launch_bounds__(256) void knn_cand_kernel(const float2 *__restrict_
     int i0 = min(max(cr[lane], 0), n_per - 1), i1 = min(max(cr[64 + lane], 0), n_per - 1);
     key_t k0 = 0, k1 = 0;
     bool sorted = false, tie = false;  // tie: as knn_finish's (QUERY)
+    // Select before sorting.  The candidates come in the unmoved mesh's
+    // distance order and the mesh moves little, so U = the largest moved fp32
+    // key among the first kk candidates bounds the kk-th smallest key tightly:
+    // kk candidates have key <= U.  With thr = filter_threshold(U) every
+    // selected key (<= thr) is below every other, so the selected set C (m
+    // elements, kk <= m) sorted by (fp32 key, index) is the first m of the
+    // 128-wide sort; and (QUERY, the proof above filter_threshold) every point
+    // whose fp64 key is at most the kk-th smallest fp64 key is in C, so C
+    // sorted by (fp64 key, index) starts with the 128-wide sort's first kk,
+    // followed by a point that ties rank kk - 1 whenever one exists.  With
+    // m <= 64, C is packed one per lane -- the selected second-register
+    // elements move into unselected first-register lanes through this wave's
+    // LDS list (written at their rank, read by free-lane rank: no atomics, the
+    // same packing whatever the schedule), the other lanes get the maximal key
+    // -- and sorted by the 64-wide one-register network: 21 compare-exchange
+    // stages on one (key, index) pair instead of 27 on two.  Lanes < m then
+    // hold what the 128-wide sort leaves there.  m > 64: the 128-wide sort.
+    __shared__ uint32_t sMoveF[4][64];
+    __shared__ int sMoveI[4][64];
+    const uint32_t f0 = key_f32(X[i0], q), f1 = key_f32(X[i1], q);
+    const uint32_t thr = KT::filter_threshold(wave_umax(lane < kk ? f0 : 0u, lane));
+    const bool s0 = f0 <= thr, s1 = f1 <= thr;
+    const uint64_t b0 = __ballot(s0), b1 = __ballot(s1);
+    const int m1 = __popcll(b1), m = __popcll(b0) + m1;
+    const bool narrow = m <= 64;  // wave-uniform
+    uint32_t cf = s0 ? f0 : 0xffffffffu;  // C, one per lane: fp32 key (maximal: none) and index
+    int ci = i0;                          // (always a valid point index)
+    if (narrow) {
+        const int wv = threadIdx.x >> 6;
+        const uint32_t lo0 = (uint32_t)b0, hi0 = (uint32_t)(b0 >> 32), lo1 = (uint32_t)b1, hi1 = (uint32_t)(b1 >> 32);
+        if (s1) {
+            const int r = (int)__builtin_amdgcn_mbcnt_hi(hi1, __builtin_amdgcn_mbcnt_lo(lo1, 0u));
+            sMoveF[wv][r] = f1;
+            sMoveI[wv][r] = i1;
+        }
+        wave_lds_sync();
+        const int fr = (int)__builtin_amdgcn_mbcnt_hi(~hi0, __builtin_amdgcn_mbcnt_lo(~lo0, 0u));
+        if (!s0 && fr < m1) {
+            cf = sMoveF[wv][fr];
+            ci = sMoveI[wv][fr];
+        }
+    }
     if constexpr (QUERY) if (kk < 64) {
         // sklearn's fp64 order, found by the cheaper fp32 (key, index) sort and
         // checked exactly: ranks 0 .. kk-1 must be in fp64 (key, index) order
@@ -898,14 +954,18 @@ __global__ __launch_bounds__(256) void knn_cand_kernel(const float2 *__restrict_
         // (KeyTraits<true>::filter_threshold: the fp32 key is within 2^-22
         // relative of the fp64 one), so no later candidate's fp64 key can be
         // below rank kk-1's.  Otherwise (ties, near-ties) the fp64 sort below.
-        uint32_t f0 = key_f32(X[i0], q), f1 = key_f32(X[i1], q);
-        int j0 = i0, j1 = i1;
-        wave_sort128(f0, j0, f1, j1, lane);
+        uint32_t g0 = narrow ? cf : f0, g1 = f1;
+        int j0 = narrow ? ci : i0, j1 = i1;
+        if (narrow) wave_sort64_ki(g0, j0, lane);
+        else wave_sort128(g0, j0, g1, j1, lane);
         const uint64_t e0 = KT::key(X[j0], q);
         const uint64_t en = __shfl(e0, (lane + 1) & 63, 64);
         const int jn = __shfl(j0, (lane + 1) & 63, 64);
         const bool pair_ok = lane >= kk - 1 || ki_less(e0, j0, en, jn);
-        const uint32_t fk = lane_value(f0, kk), fk1 = lane_value(f0, kk - 1);
+        // rank kk's fp32 key: with m == kk it is not in C but the smallest key outside it
+        const uint32_t fk = m == kk ? wave_umin(min(s0 ? 0xffffffffu : f0, s1 ? 0xffffffffu : f1), lane)
+                                    : lane_value(g0, kk);
+        const uint32_t fk1 = lane_value(g0, kk - 1);
         if (__ballot(!pair_ok) == 0ull && fk > KT::filter_threshold(fk1)) {
             k0 = e0;
             i0 = j0;
@@ -914,7 +974,19 @@ __global__ __launch_bounds__(256) void knn_cand_kernel(const float2 *__restrict_
             tie = __ballot(lane < kk - 1 && e0 == en) != 0ull;
         }
     }
-    if (!sorted) {
+    if (!sorted && narrow) {
+        // C by exact key.  Rank kk, when m > kk, sits in lane kk; with m == kk no
+        // point outside C ties rank kk - 1 (QUERY: its fp32 key exceeds the
+        // filter margin over every selected one's), so lane kk - 1 reports none.
+        i0 = ci;
+        if constexpr (QUERY) k0 = cf == 0xffffffffu ? ~key_t(0) : KT::key(X[ci], q);
+        else k0 = cf;
+        wave_sort64_ki(k0, i0, lane);
+        if (QUERY) {
+            const key_t n0 = (key_t)__shfl((unsigned long long)k0, (lane + 1) & 63, 64);
+            tie = __ballot(lane < kk && lane + 1 < m && k0 == n0) != 0ull;
+        }
+    } else if (!sorted) {
         k0 = KT::key(X[i0], q);
         k1 = KT::key(X[i1], q);
         wave_sort128(k0, i0, k1, i1, lane);

@@ -501,6 +501,10 @@ struct NodeArgs {
     const int32_t *div_deg = nullptr;
     int div_k = 0;
     EdgeSplit split;       // units > 0: add the wave kernel's side blocks first
+    // HEAD (last layer): the Conv1d output head of the tile's rows -> out [n, tw];
+    // h_out may then be nullptr (h' is not stored)
+    mmpde_gnn_head_params head{};
+    float *out = nullptr;
 };
 
 constexpr int NLD = 132;  // fp32 staging row stride (floats)
@@ -875,8 +879,104 @@ __device__ uint64_t *g_node_stamps;
     } while (0)
 #endif
 
-template <bool NEXT, bool F16X3>
+// Conv1d output head (gnn_2d.py:108-114,136-139; gnn.hip head_kernel) of the
+// tile's ROWS rows of h' in stage (row stride NLD), fused into the last
+// layer's node kernel: 128 -> conv(1->4, k16, s3) 38 -> relu -> conv(4->8,
+// k12, s3) -> relu -> conv(8->1, k8, s2) 1, times the output scale(s).  Every
+// output runs head_kernel's fmaf chain in head_kernel's order, so the result is
+// bit for bit the separate launch's.  scr (the dead operand image) holds the
+// conv0 outputs y1 [row][4][38] and the relu'd conv2 outputs y2 [row][8][8]
+// (only conv2's first 8 outputs feed conv4).  Weights are wave-uniform (scalar
+// loads) in conv0 and conv2.  Starts with the barrier that publishes stage.
+constexpr int HY1 = 4 * 38 + 1;  // y1 row stride (floats): odd, rows on distinct banks
+constexpr int HY2 = 8 * 8 + 1;   // y2 row stride (floats)
+static_assert(ROWS == 32 && ROWS * (HY1 + HY2) <= RB * 16 * 64 * 4, "head scratch fits the operand image");
+
+__device__ __forceinline__ void head_phase(const mmpde_gnn_head_params &hp, const float *stage, float *scr,
+                                           int64_t row0, int64_t n, float *__restrict__ out, int tid) {
+    float *const y1 = scr, *const y2 = scr + ROWS * HY1;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int row = lane & 31, hi = lane >> 5;
+    __syncthreads();  // h' rows staged; every wave is done with the operand image
+    {   // conv0: wave -> channel c and half of the 19 output pairs, lane -> (row, quarter)
+        const int c = wave & 3;
+        const int q_begin = 10 * (2 * (wave >> 2) + hi);  // outputs [0, 10) [10, 20) [20, 30) [30, 38)
+        float w[16];
+#pragma unroll
+        for (int t = 0; t < 16; ++t) w[t] = hp.c0_w[c * 16 + t];
+        const float b = hp.c0_b[c];
+        const float *hr = stage + row * NLD;
+        float *yr = y1 + row * HY1 + c * 38;
+#pragma unroll
+        for (int j = 0; j < 10; j += 2) {
+            const int q0 = q_begin + j;
+            if (q0 < 38) {
+                float x[19];
+#pragma unroll
+                for (int i = 0; i < 19; ++i) x[i] = hr[3 * q0 + i];
+#pragma unroll
+                for (int qq = 0; qq < 2; ++qq) {
+                    float v = b;
+#pragma unroll
+                    for (int t = 0; t < 16; ++t) v = fmaf(w[t], x[3 * qq + t], v);
+                    yr[q0 + qq] = fmaxf(v, 0.0f);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    {   // conv2: wave -> channel co, lane -> (row, outputs 4 hi .. 4 hi + 3)
+        const int co = wave;
+        float acc[4];
+        const float b = hp.c2_b[co];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = b;
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) {
+            float y[21], w[12];
+            const float *yr = y1 + row * HY1 + ci * 38 + 12 * hi;
+#pragma unroll
+            for (int i = 0; i < 21; ++i) y[i] = yr[i];
+#pragma unroll
+            for (int t = 0; t < 12; ++t) w[t] = hp.c2_w[(co * 4 + ci) * 12 + t];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+#pragma unroll
+                for (int t = 0; t < 12; ++t) acc[q] = fmaf(w[t], y[3 * q + t], acc[q]);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) y2[row * HY2 + co * 8 + 4 * hi + q] = fmaxf(acc[q], 0.0f);
+    }
+    __syncthreads();
+    if (wave < 2) {  // conv4: lane -> (row, channel pair c): the pair's chain, then the row's 4 lanes meet
+        const int r2 = 16 * wave + (lane >> 2), c = lane & 3;
+        float part = 0.0f;
+#pragma unroll
+        for (int oo = 0; oo < 2; ++oo) {
+            const int co = 2 * c + oo;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) part = fmaf(hp.c4_w[co * 8 + t], y2[r2 * HY2 + co * 8 + t], part);
+        }
+        const float s0 = __shfl(part, (lane & ~3), 64), s1 = __shfl(part, (lane & ~3) + 1, 64);
+        const float s2 = __shfl(part, (lane & ~3) + 2, 64), s3 = __shfl(part, (lane & ~3) + 3, 64);
+        const int64_t grow = row0 + r2;
+        if (c == 0 && grow < n) {
+            const float diff = hp.c4_b[0] + ((s0 + s1) + (s2 + s3));
+            if (hp.tw <= 1) {
+                out[grow] = hp.out_scale * diff;
+            } else {  // out [n, tw] = cumsum(dt) * diff (gnn_2d.py:137-141)
+                for (int t = 0; t < hp.tw; ++t) out[grow * hp.tw + t] = hp.out_scales[t] * diff;
+            }
+        }
+    }
+}
+
+// HEAD (the last layer, NEXT false): the output head of the tile's rows runs
+// after the epilogue (head_phase) and h' is stored only when h_out != nullptr.
+template <bool NEXT, bool F16X3, bool HEAD = false>
 __global__ __launch_bounds__(512, NODE_WPE) void gnn_node_kernel(NodeArgs p) {
+    static_assert(!(NEXT && HEAD), "the head follows the last layer");
     NODE_STAMP(0);
     __shared__ float4 img[RB * 16 * 64];        // operand image, K = 256 (h | mean), then 128
     __shared__ float stage[ROWS * NLD];         // fp32 v, then h'
@@ -963,6 +1063,7 @@ __global__ __launch_bounds__(512, NODE_WPE) void gnn_node_kernel(NodeArgs p) {
         // flight over the epilogue and the prep
         if (NEXT) bA.load(p.pkn + kPkW1, 4, wave, 0, w1r, 0, lane);
         const bool full = row0 + ROWS <= p.n;
+        const bool keep = !HEAD || p.h_out != nullptr;  // HEAD: h' is stored only on request
         float *hp = p.h_out + (row0 + 4 * g) * LH + col;
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
@@ -973,8 +1074,8 @@ __global__ __launch_bounds__(512, NODE_WPE) void gnn_node_kernel(NodeArgs p) {
                 if (F16X3) z = z * pow2_inv(rs[2][lr]) * u2_is;
                 const float x = hres[lr * NLD + col] + fmaxf(z + u2_b, 0.0f);
                 const float y = bn(x);
-                if (full || row0 + lr < p.n) hp[(16 * rb + q) * LH] = y;
-                if (NEXT) stage[lr * NLD + col] = y;
+                if (keep && (full || row0 + lr < p.n)) hp[(16 * rb + q) * LH] = y;
+                if (NEXT || HEAD) stage[lr * NLD + col] = y;
             }
         }
     }
@@ -988,6 +1089,7 @@ __global__ __launch_bounds__(512, NODE_WPE) void gnn_node_kernel(NodeArgs p) {
         proj_phase<F16X3>(bA, img, rs[3], &rowv[0][0], w1c, p.pkn, w1r, tw, row0, p.n, p.seg_n,
                               p.a_out, p.b_out, p.rmx_out, &rng_arrived, wave, lane);
     }
+    if constexpr (HEAD) head_phase(p.head, stage, (float *)img, row0, p.n, p.out, tid);
     NODE_STAMP(7);
 }
 
@@ -1273,13 +1375,14 @@ int launch_node_stage(const float *h, const float *mean, const EdgeSplit *split,
                       const float *u, const float *pos, int64_t n, int64_t seg_n, mmpde_gnn_scales sc,
                       const mmpde_gnn_layer_params *p, const mmpde_gnn_layer_params *next,
                       const char *pk, const char *pkn, float *rmx_out, float *h_out, float *a_out,
-                      float *b_out, hipStream_t st) {
+                      float *b_out, hipStream_t st, const mmpde_gnn_head_params *head, float *out) {
     const bool sums = split && split->units > 0;
     MMPDE_REQUIRE(!sums || (split->side && split->S > 0 && split->k > 0 && split->seg_n > 0 &&
                             n % split->seg_n == 0));
     MMPDE_REQUIRE(!rmx_out || al16(rmx_out));
-    MMPDE_REQUIRE(h && mean && u && pos && p && h_out && n > 0);
+    MMPDE_REQUIRE(h && mean && u && pos && p && (h_out || head) && n > 0);
     MMPDE_REQUIRE(al16(h) && al16(mean) && al16(h_out));
+    MMPDE_REQUIRE(!head || (!next && out && head->tw <= MAX_TW && (head->tw <= 1 || head->out_scales)));
     MMPDE_REQUIRE(p->upd1_ld >= 257 && (p->upd1_ld & 3) == 0 && al16(p->upd1_w) && al16(p->upd2_w));
     MMPDE_REQUIRE(!pk || (al16(pk) && (!next || pkn)));
     NodeArgs a{h, mean, n, p->upd1_w, p->upd1_b, p->upd1_ld, p->upd2_w, p->upd2_b, p->bn_w, p->bn_b,
@@ -1287,6 +1390,10 @@ int launch_node_stage(const float *h, const float *mean, const EdgeSplit *split,
                pk, pkn, rmx_out, effective_seg(n, seg_n), sums ? deg : nullptr,
                sums ? split->k : 0};
     if (sums) a.split = *split;
+    if (head) {
+        a.head = *head;
+        a.out = out;
+    }
     if (next) {
         MMPDE_REQUIRE(a_out && b_out && next->msg1_ld >= 260 && (next->msg1_ld & 3) == 0 &&
                       al16(next->msg1_w));
@@ -1298,11 +1405,13 @@ int launch_node_stage(const float *h, const float *mean, const EdgeSplit *split,
     MMPDE_REQUIRE(tiles < (int64_t)INT32_MAX);
     const dim3 grid((unsigned)tiles);
     const bool f16 = pk != nullptr;
-#define MMPDE_NODE(NX, F16) hipLaunchKernelGGL((gnn_node_kernel<NX, F16>), grid, dim3(512), 0, st, a)
-    if (next && f16) MMPDE_NODE(true, true);
-    else if (next) MMPDE_NODE(true, false);
-    else if (f16) MMPDE_NODE(false, true);
-    else MMPDE_NODE(false, false);
+#define MMPDE_NODE(NX, F16, HD) hipLaunchKernelGGL((gnn_node_kernel<NX, F16, HD>), grid, dim3(512), 0, st, a)
+    if (next && f16) MMPDE_NODE(true, true, false);
+    else if (next) MMPDE_NODE(true, false, false);
+    else if (head && f16) MMPDE_NODE(false, true, true);
+    else if (head) MMPDE_NODE(false, false, true);
+    else if (f16) MMPDE_NODE(false, true, false);
+    else MMPDE_NODE(false, false, false);
 #undef MMPDE_NODE
     MMPDE_RET_LAUNCH();
     return MMPDE_OK;

@@ -177,11 +177,16 @@ int launch_edge_wave(const float *a, const float *b, const int32_t *nbr, const i
 // next != nullptr, the next layer's message_net_1 node halves a', b' (and,
 // F16X3, their row maxima and range records rmx_out, row_records_floats(n)).
 // F16X3 when pk != nullptr (pkn: the next layer's images).
+// head != nullptr (the last layer: next must be nullptr): the kernel also
+// runs the Conv1d output head on the tile's rows of h' while they are in LDS
+// and writes out [n, tw], bit for bit mmpde_gnn_head's; h' itself is stored
+// only when h_out != nullptr.
 int launch_node_stage(const float *h, const float *mean, const EdgeSplit *split, const int32_t *deg,
                       const float *u, const float *pos, int64_t n, int64_t seg_n, mmpde_gnn_scales sc,
                       const mmpde_gnn_layer_params *p, const mmpde_gnn_layer_params *next,
                       const char *pk, const char *pkn, float *rmx_out, float *h_out, float *a_out,
-                      float *b_out, hipStream_t st);
+                      float *b_out, hipStream_t st, const mmpde_gnn_head_params *head = nullptr,
+                      float *out = nullptr);
 
 // Embedding (gnn_2d.py:99-106) + layer 0's message_net_1 node halves in one
 // launch: h_out = embedding_mlp(cat(u, x/Lx, y/Ly, t/tmax)), a_out / b_out as

@@ -13,7 +13,7 @@ import os
 import torch
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmmpde_hip.so")
-ABI_VERSION = 12100
+ABI_VERSION = 12200
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_ELU = 0, 1, 2, 3
 PAD_ZEROS, PAD_CIRCULAR = 0, 1
@@ -63,7 +63,7 @@ class GnnExec(ctypes.Structure):
     """mmpde_gnn_exec: optional per-layer hipEvents + the edge-GEMM arithmetic."""
     _fields_ = [("edge_begin", ctypes.POINTER(_P)), ("edge_end", ctypes.POINTER(_P)),
                 ("edge_gemm", _I), ("packed", _P), ("node_end", ctypes.POINTER(_P)),
-                ("degree", _P), ("seg_n", _I64)]
+                ("degree", _P), ("seg_n", _I64), ("h_last", _P)]
 
 
 class DmmGraphBranch(ctypes.Structure):
