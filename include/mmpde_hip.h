@@ -60,8 +60,10 @@ const char *mmpde_status_string(int status);
  *          [nbr_out.flatten(), repeat_interleave(arange(n), k)].
  * degenerate (nullable, device int32[1], accumulated): queries whose degree
  *          would be ragged in the reference (self not among the k+1 nearest).
- * Requires k+1 <= n_per <= 16384, k <= 63 (more than 4096 points per
- * trajectory: a slower path with the points in a 128 KB LDS block). */
+ * Requires k+1 <= n_per <= 65536, k <= 63 (more than 4096 points per
+ * trajectory: a slower path with the points in a 128 KB LDS block).  More
+ * than 16384: the tiled path, which streams the points through LDS in tiles
+ * of 4096, twice, and needs batches * n_per <= INT32_MAX; the same output. */
 int mmpde_knn_graph(const float *pos, int64_t batches, int64_t n_per, int k,
                     int32_t *nbr_out, int32_t *degenerate, mmpde_stream_t stream);
 
@@ -111,7 +113,8 @@ int mmpde_knn_table_misses(const float *cells, int64_t batches, int32_t *misses_
  * whose median cell displacement (over the record's non-empty cells) exceeds
  * it goes straight to the full search (mmpde_knn_skip_threshold); <= 0: the
  * table is always tried.  k <= 63 and 128 <= n_per <= 4096, else it
- * is mmpde_knn_graph. */
+ * is mmpde_knn_graph.  That includes its tiled path for 16384 < n_per <=
+ * 65536, where no candidate table exists. */
 int64_t mmpde_knn_graph_cand_scratch_bytes(int64_t batches, int64_t n_per);
 int mmpde_knn_graph_cand(const float *pos, const float *xi, const float *cells, float skip_above,
                          int64_t batches, int64_t n_per, int k, const int32_t *cand, int32_t *nbr_out,
@@ -127,7 +130,9 @@ int mmpde_knn_graph_cand(const float *pos, const float *xi, const float *cells, 
  * between ranks k-1 and k -- the only inputs on which sklearn's own order (its
  * KD-tree traversal) may differ from (distance, index); parity with sklearn is
  * unpinned for those queries.
- * Requires k <= n_src <= 16384, k <= 63. */
+ * Requires k <= n_src <= 65536, k <= 63.  More than 16384 source points:
+ * the tiled path of mmpde_knn_graph (batches * n_src <= INT32_MAX), the same
+ * output and the same ties count. */
 int mmpde_knn_query(const float *src, const float *qry, int64_t batches, int64_t n_src,
                     int64_t n_qry, int k, int32_t *idx_out, int32_t *ties, mmpde_stream_t stream);
 
@@ -141,7 +146,8 @@ int mmpde_knn_query(const float *src, const float *qry, int64_t batches, int64_t
  * mmpde_knn_moved_cells(src, xi).  n_src = n_qry = n_per; scratch as for
  * mmpde_knn_graph_cand; ties as for mmpde_knn_query (each query counted
  * once, by whichever kernel answered it).  k <= 64 and 128 <= n_per <= 4096,
- * else it is mmpde_knn_query. */
+ * else it is mmpde_knn_query.  That includes its tiled path for 16384 < n_per
+ * <= 65536. */
 int mmpde_knn_query_cand(const float *src, const float *qry, const float *xi, const float *ref,
                          const float *cells, float skip_above, int64_t batches, int64_t n_per, int k,
                          const int32_t *cand, int32_t *idx_out, int32_t *ties, void *scratch,

@@ -5,7 +5,8 @@
 // (data_creator_2d.py:66-78).  One wave per query; the trajectory's point set
 // (<= 4096 points, <= 32 KB) is staged once per workgroup in LDS; every lane
 // keeps CPL fp32 squared distances in registers (larger sets, up to 16384
-// points: knn_large_kernel below).  Selection: U = the kk-th
+// points: knn_large_kernel below; up to 65536: knn_tiled_kernel, which streams
+// the set through LDS in tiles).  Selection: U = the kk-th
 // smallest of the 64 per-lane minima (a 64-wide bitonic sort across the wave)
 // bounds the kk-th smallest key from above; the points with key <= U (a few
 // dozen on a mesh; for the fp64 query key, fp32 key <= U plus a proven
@@ -606,18 +607,223 @@ int launch_knn_large(const float2 *p, const float2 *q, int64_t batches, int ns, 
     return MMPDE_OK;
 }
 
+// Trajectories of more than kLargeMax points (up to kTiledMax, a 256 x 256
+// grid): the set no longer fits one CU's LDS, so it streams through a tile of
+// kTile points, twice -- pass 1 the lane minima of the fp32 filter key over
+// every tile, then thr exactly as above (the bound "at least kk points have
+// key <= U" counts one point per lane, however the points were cut into
+// tiles: every point is still seen by exactly one lane); pass 2 the
+// compaction of C = {key <= thr} into one LDS list per query, its true size m
+// counted past kCap.  Then knn_finish with the trajectory's global
+// pointer in place of the LDS copy: candidate coordinates and the overflow
+// path's radix select read global memory (rare, slow, exact; (key, index)
+// order does not know about tiles).  Same results as knn_large_kernel.
+// A wave owns kTiledQW queries for the whole kernel: their minima, thresholds
+// and list sizes live in registers across the tiles (compile-time indices:
+// the query loops are unrolled), and every point read from LDS is applied to
+// kTiledQB of them, so the kernel is bound by the key arithmetic and not by
+// one ds_read_b64 per key.  75 KB of LDS: two workgroups per CU.
+// Which lane sees which point is free (the bound needs a partition, nothing
+// more), and it decides how tight U is: with lane = j % 64, a row-major
+// lattice whose width is a multiple of 64 (128 x 128, 192 x 192, 256 x 256)
+// puts a whole grid line on one lane, the 36 nearest lanes then reach 18 cells
+// out, C holds ~1000 points and EVERY query overflows into the radix select.
+// So column c of a tile is rotated by c lanes (tiled_point): neighbouring grid
+// lines fall on different lanes and C is ~80-110 points on those lattices.
+constexpr int kTiledMax = 65536;
+constexpr int kTile = 4096;                    // points: 64 columns x 64 lanes, one mask bit per column
+constexpr int kTiledQueries = 32;              // per workgroup
+constexpr int kTiledQW = kTiledQueries / 4;    // per wave
+constexpr int kTiledQB = 4;                    // queries per loaded point
+static_assert(kTile == 64 * 64 && kTile <= kLargeMax && kTiledQW % kTiledQB == 0, "knn_tiled_kernel's shape");
+// dynamic LDS: tile | lists [kTiledQueries][kCap] | sKey [4][kCap] (8-byte keys) | sSel [4][64] | q, m per query
+constexpr int kTiledOffList = kTile * 8;
+constexpr int kTiledOffKey = kTiledOffList + kTiledQueries * kCap * 4;
+constexpr int kTiledOffSel = kTiledOffKey + 4 * kCap * 8;
+constexpr int kTiledOffQ = kTiledOffSel + 4 * 64 * 4;
+constexpr int kTiledOffM = kTiledOffQ + kTiledQueries * 8;
+constexpr int kTiledLds = kTiledOffM + kTiledQueries * 4;
+
+// Tile-local index of the point that lane `lane` reads in column c (slot
+// lane + 64 c of the tile): column c rotated by c lanes.
+__device__ __forceinline__ int tiled_point(int lane, int c) { return 64 * c + ((lane - c) & 63); }
+
+// One tile's candidates of one query (bit c of cm: the point of column c on
+// this lane) appended to its list at m, in any order (knn_large_kernel's
+// prefix of the per-lane counts); most tiles hold none.
+__device__ __forceinline__ void tiled_append(uint64_t cm, int t0, int *list, int &m, int lane, uint64_t below) {
+    if (__ballot(cm != 0ull) == 0ull) return;  // wave-uniform
+    const int cnt = __popcll(cm);
+    int tot = 0, pidx = m;
+#pragma unroll
+    for (int bit = 0; bit < 7; ++bit) {  // cnt <= 64 < 2^7
+        const uint64_t plane = __ballot((cnt >> bit) & 1);
+        tot += __popcll(plane) << bit;
+        pidx += __popcll(plane & below) << bit;
+    }
+    while (cm) {
+        const int c = __builtin_ctzll(cm);
+        cm &= cm - 1;
+        if (pidx < kCap) list[pidx] = t0 + tiled_point(lane, c);
+        ++pidx;
+    }
+    m += tot;
+}
+
+template <bool QUERY>
+__global__ __launch_bounds__(256, 2) void knn_tiled_kernel(const float2 *__restrict__ pts,
+                                                           const float2 *__restrict__ qry, int n_src,
+                                                           int n_q, int k, int32_t *__restrict__ out,
+                                                           int32_t *__restrict__ degenerate) {
+    typedef KeyTraits<QUERY> KT;
+    typedef typename KT::key_t key_t;
+    extern __shared__ __attribute__((aligned(16))) unsigned char tiled_lds[];
+    float2 *sT = (float2 *)tiled_lds;
+
+    const int b = blockIdx.y;
+    const float2 *P = pts + (int64_t)b * n_src;
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int kk = QUERY ? k : k + 1;
+    const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const int qbase = (int)blockIdx.x * kTiledQueries + wave * kTiledQW;
+    int *lists = (int *)(tiled_lds + kTiledOffList) + wave * kTiledQW * kCap;
+    float2 *sQ = (float2 *)(tiled_lds + kTiledOffQ) + wave * kTiledQW;
+    int *sM = (int *)(tiled_lds + kTiledOffM) + wave * kTiledQW;
+
+    // queries past n_q (the last workgroup) repeat the last one and are not written
+    float2 q[kTiledQW];
+    uint32_t lmin[kTiledQW];
+#pragma unroll
+    for (int u = 0; u < kTiledQW; ++u) {
+        const int qi = min(qbase + u, n_q - 1);
+        q[u] = QUERY ? qry[(int64_t)b * n_q + qi] : P[qi];
+        lmin[u] = ~0u;
+    }
+    // A tile goes global -> registers -> LDS, and the next tile's loads are
+    // issued before the current one is searched, so they land behind its
+    // arithmetic.  The last tile's unused slots take the previous tile's points
+    // of the same slot, hence the same lane (n_src > kTile): a lane's minimum
+    // over its own points with one repeated is its minimum, so pass 1 tests no
+    // bound; pass 2 masks those slots out (valid).
+    float2 nxt[kTile / 256];
+    auto fetch = [&](int t0) {
+        const int tn = min(kTile, n_src - t0);
+#pragma unroll
+        for (int i = 0; i < kTile / 256; ++i) {
+            const int j = (int)threadIdx.x + 256 * i;
+            nxt[i] = P[j < tn ? t0 + j : t0 + j - kTile];
+        }
+    };
+    auto stage = [&](int t0) {
+        __syncthreads();  // the previous tile's readers
+#pragma unroll
+        for (int i = 0; i < kTile / 256; ++i) {
+            const int j = (int)threadIdx.x + 256 * i;  // column j >> 6, rotated by as many lanes
+            sT[(j & ~63) + ((j + (j >> 6)) & 63)] = nxt[i];
+        }
+        __syncthreads();
+        if (t0 + kTile < n_src) fetch(t0 + kTile);
+    };
+    fetch(0);
+    for (int t0 = 0; t0 < n_src; t0 += kTile) {
+        stage(t0);
+#pragma unroll
+        for (int g = 0; g < kTiledQW; g += kTiledQB) {
+#pragma unroll 8
+            for (int c = 0; c < kTile / 64; ++c) {
+                const float2 p = sT[lane + 64 * c];
+#pragma unroll
+                for (int u = 0; u < kTiledQB; ++u) {
+                    const uint32_t f = key_f32(p, q[g + u]);
+                    lmin[g + u] = f < lmin[g + u] ? f : lmin[g + u];
+                }
+            }
+        }
+    }
+    fetch(0);  // pass 2's first tile, behind the sorts
+    uint32_t thr[kTiledQW];
+    int m[kTiledQW];
+#pragma unroll
+    for (int u = 0; u < kTiledQW; ++u) {
+        thr[u] = KT::filter_threshold(lane_value(wave_sort64(lmin[u], lane), kk - 1));
+        m[u] = 0;
+    }
+    for (int t0 = 0; t0 < n_src; t0 += kTile) {
+        const int tn = min(kTile, n_src - t0);
+        stage(t0);
+        uint64_t valid = ~0ull;  // bit c: this lane's slot of column c holds a point of this tile
+        if (tn < kTile) {
+            valid = 0ull;
+            for (int c = 0; c < kTile / 64; ++c) valid |= (uint64_t)(tiled_point(lane, c) < tn) << c;
+        }
+#pragma unroll
+        for (int g = 0; g < kTiledQW; g += kTiledQB) {
+            uint64_t cm[kTiledQB];
+#pragma unroll
+            for (int u = 0; u < kTiledQB; ++u) cm[u] = 0ull;
+            for (int c0 = 0; c0 < kTile / 64; c0 += 8) {
+                uint32_t w[kTiledQB];
+#pragma unroll
+                for (int u = 0; u < kTiledQB; ++u) w[u] = 0u;
+#pragma unroll
+                for (int cc = 0; cc < 8; ++cc) {
+                    const float2 p = sT[lane + 64 * (c0 + cc)];
+#pragma unroll
+                    for (int u = 0; u < kTiledQB; ++u)
+                        w[u] |= (uint32_t)(key_f32(p, q[g + u]) <= thr[g + u]) << cc;
+                }
+#pragma unroll
+                for (int u = 0; u < kTiledQB; ++u) cm[u] |= (uint64_t)w[u] << c0;
+            }
+#pragma unroll
+            for (int u = 0; u < kTiledQB; ++u) tiled_append(cm[u] & valid, t0, lists + (g + u) * kCap, m[g + u], lane, below);
+        }
+    }
+    // one copy of the selection code: the per-query registers go through LDS
+#pragma unroll
+    for (int u = 0; u < kTiledQW; ++u)
+        if (lane == 0) {
+            sQ[u] = q[u];
+            sM[u] = m[u];
+        }
+    wave_lds_sync();
+    const int cpl = (n_src + 63) / 64;
+#pragma unroll 1
+    for (int u = 0; u < kTiledQW && qbase + u < n_q; ++u)
+        knn_finish<QUERY>(P, (key_t *)(tiled_lds + kTiledOffKey) + wave * kCap, lists + u * kCap,
+                          (int *)(tiled_lds + kTiledOffSel) + wave * 64, sM[u], sQ[u], kk, k, qbase + u, b, n_src,
+                          n_q, cpl, lane, below, out, degenerate);
+}
+
+template <bool QUERY>
+int launch_knn_tiled(const float2 *p, const float2 *q, int64_t batches, int ns, int nq, int k, int32_t *out,
+                     int32_t *degenerate, hipStream_t st) {
+    const hipError_t e =
+        hipFuncSetAttribute((const void *)knn_tiled_kernel<QUERY>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            kTiledLds);
+    if (e != hipSuccess) return MMPDE_ERR_HIP_BASE - (int)e;
+    dim3 grid(ceil_div(nq, kTiledQueries), (unsigned)batches);
+    hipLaunchKernelGGL(knn_tiled_kernel<QUERY>, grid, dim3(256), kTiledLds, st, p, q, ns, nq, k, out, degenerate);
+    MMPDE_RET_LAUNCH();
+    return MMPDE_OK;
+}
+
 template <bool QUERY>
 int launch_knn(const float *pts, const float *qry, int64_t batches, int64_t n_src, int64_t n_q,
                int k, int32_t *out, int32_t *degenerate, hipStream_t st) {
     const int kk = QUERY ? k : k + 1;
-    if (k < 1 || kk > 64 || n_src < kk || n_src > kLargeMax || n_q < 1 || batches < 1 ||
+    if (k < 1 || kk > 64 || n_src < kk || n_src > kTiledMax || n_q < 1 || batches < 1 ||
         batches > 65535 || n_q > INT32_MAX / 64)
         return MMPDE_ERR_INVALID_ARG;
+    // the graph's indices are global int32
+    if (n_src > kLargeMax && batches * n_src > INT32_MAX) return MMPDE_ERR_INVALID_ARG;
     dim3 grid(ceil_div(n_q, kQueriesPerBlock), (unsigned)batches);
     const int cpl = ceil_div(n_src, 64);
     const float2 *p = (const float2 *)pts;
     const float2 *q = (const float2 *)qry;
     const int ns = (int)n_src, nq = (int)n_q;
+    if (n_src > kLargeMax) return launch_knn_tiled<QUERY>(p, q, batches, ns, nq, k, out, degenerate, st);
     if (n_src > 4096) return launch_knn_large<QUERY>(p, q, batches, ns, nq, k, out, degenerate, st);
 #define MMPDE_KNN_CASE(C)                                                                     \
     if (cpl <= C) {                                                                           \

@@ -14,18 +14,20 @@ import torch
 from . import _lib as L
 from . import rows
 
-# kNN kernels stage one trajectory's points in LDS and keep its distances in
-# registers (csrc/knn.hip): at most this many points per trajectory
-# (include/mmpde_hip.h mmpde_knn_graph / mmpde_knn_query).  The reference's
-# benchmarked grids are 2521 (cy) and 48 x 48 = 2304 (burgers); burgers at the
-# PDE's own default 96 x 96 (PDEs.py:27) exceeds it.
-KNN_MAX_POINTS = 16384
+# kNN kernels search one trajectory's points from LDS (csrc/knn.hip): the whole
+# set staged at once up to 16384 points, streamed in tiles of KNN_TILE_POINTS
+# above that, up to KNN_MAX_POINTS per trajectory (include/mmpde_hip.h
+# mmpde_knn_graph / mmpde_knn_query).  The reference's benchmarked grids are
+# 2521 (cy) and 48 x 48 = 2304 (burgers); burgers at the PDE's own default
+# 96 x 96 (PDEs.py:27) and at its data's native 192 x 192 (mmpde.py:171) fit.
+KNN_MAX_POINTS = 65536
+KNN_TILE_POINTS = 4096  # kTile in csrc/knn.hip
 
 
 def _knn_points_check(n_per: int, k: int, what: str):
     if n_per > KNN_MAX_POINTS:
         raise ValueError(f"{what}: {n_per} points per trajectory; the HIP kNN kernels take at "
-                         f"most {KNN_MAX_POINTS} (run --base_resolution <= 128 x 128)")
+                         f"most {KNN_MAX_POINTS} (run --base_resolution <= 256 x 256)")
     if k > 63:
         raise ValueError(f"{what}: k = {k}; the HIP kNN kernels take k <= 63")
 
