@@ -153,6 +153,42 @@ int mmpde_knn_query_cand(const float *src, const float *qry, const float *xi, co
                          const int32_t *cand, int32_t *idx_out, int32_t *ties, void *scratch,
                          mmpde_stream_t stream);
 
+/* Cell-binned exact kNN: the searches above at a cost that follows the local
+ * point density instead of n_per, for point sets that moved arbitrarily far
+ * (the grid is laid over the points as they are).
+ *
+ * mmpde_knn_bin sorts each trajectory's points src [batches * n_per, 2] into a
+ * uniform grid over that trajectory's bounding box: mmpde_knn_bins_grid(n_per)
+ * = floor(sqrt(n_per / 4)) cells per axis (at most 128; one cell on an axis of
+ * zero extent), cell = trunc((v - min) * cells / extent) clamped.  bins:
+ * 8-byte aligned device memory of mmpde_knn_bins_bytes(batches, n_per) bytes
+ * (bins_bytes: its size, checked); both sizing helpers are host arithmetic
+ * and return 0 for arguments out of range.  One binning serves any number of
+ * searches of the same source set.  1 <= n_per <= 65536.
+ *
+ * mmpde_knn_graph_binned is mmpde_knn_graph (reference data_creator_2d.py:260
+ * on the DMM's moved mesh) and mmpde_knn_query_binned is mmpde_knn_query
+ * (data_creator_2d.py:66-78) with bins = mmpde_knn_bin of pos / src: the same
+ * keys, the same (key, index) order, the same nbr_out / idx_out and the same
+ * degenerate / ties counts, bit for bit.  One wave per query scans the cells
+ * around it ring by ring until every unscanned point is provably farther than
+ * the candidate threshold, then selects as the full searches do.  Argument
+ * limits as mmpde_knn_graph / mmpde_knn_query, and batches * n_per <=
+ * INT32_MAX at every size.  Bins built for another n_per leave the output
+ * unwritten.
+ * stats (nullable, device int64[2], accumulated): [0] += source points
+ * examined, [1] += queries whose candidate list overflowed into the full
+ * select over the trajectory.  No cost when NULL. */
+int mmpde_knn_bins_grid(int64_t n_per);
+int64_t mmpde_knn_bins_bytes(int64_t batches, int64_t n_per);
+int mmpde_knn_bin(const float *src, int64_t batches, int64_t n_per, void *bins, int64_t bins_bytes,
+                  mmpde_stream_t stream);
+int mmpde_knn_graph_binned(const float *pos, const void *bins, int64_t batches, int64_t n_per, int k,
+                           int32_t *nbr_out, int32_t *degenerate, int64_t *stats, mmpde_stream_t stream);
+int mmpde_knn_query_binned(const float *src, const void *bins, const float *qry, int64_t batches,
+                           int64_t n_src, int64_t n_qry, int k, int32_t *idx_out, int32_t *ties,
+                           int64_t *stats, mmpde_stream_t stream);
+
 /* torch_cluster.radius_graph(pos, r, batch, loop=False, max_num_neighbors)
  * (data_creator_2d.py:257-258, connect_edge='radius'; r at :195 / :226) for
  * `batches` equal contiguous segments of n_per points, CUDA semantics: each

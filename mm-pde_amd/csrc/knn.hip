@@ -6,7 +6,8 @@
 // (<= 4096 points, <= 32 KB) is staged once per workgroup in LDS; every lane
 // keeps CPL fp32 squared distances in registers (larger sets, up to 16384
 // points: knn_large_kernel below; up to 65536: knn_tiled_kernel, which streams
-// the set through LDS in tiles).  Selection: U = the kk-th
+// the set through LDS in tiles; knn_binned_kernel, far below, scans only the
+// cells of a uniform grid around the query).  Selection: U = the kk-th
 // smallest of the 64 per-lane minima (a 64-wide bitonic sort across the wave)
 // bounds the kk-th smallest key from above; the points with key <= U (a few
 // dozen on a mesh; for the fp64 query key, fp32 key <= U plus a proven
@@ -1272,6 +1273,346 @@ __global__ void edge_index_kernel(const int32_t *__restrict__ nbr, int64_t n, in
     }
 }
 
+// ---------------------------------------------------------------------------
+// Cell-binned exact kNN: the cost of a query follows the local point density,
+// not the trajectory's size.  mmpde_knn_bin sorts every trajectory's points
+// into a uniform grid over their own bounding box (so it does not matter how
+// far a mesh has moved); knn_binned_kernel scans the cells around a query ring
+// by ring until a distance bound proves that no unscanned point can be a
+// candidate, then hands the candidates to knn_finish like knn_tiled_kernel.
+//
+// Workspace, per trajectory (4-byte words, stride even so that every float2
+// stays 8-byte aligned): header [kBinHdr] | sorted points float2 [n_per] |
+// their original local indices [n_per] | cell starts [G G + 1] | cell cursors
+// [G G] (the counts, then the scatter positions).  Header: x0, y0, hx, hy,
+// 1/hx, 1/hy, eps, gx, gy (the grid actually used: G per axis, 1 on an axis
+// of zero or non-finite extent), n_per.
+// ---------------------------------------------------------------------------
+constexpr int kBinHdr = 16;
+constexpr int kBinGMax = 128;      // 65536 points at kBinPerCell
+constexpr int kBinPerCell = 4;     // points per cell the grid is sized for
+constexpr int kBinThreads = 1024;
+
+// cells per axis for a trajectory of n_per points: floor(sqrt(n_per / kBinPerCell))
+__host__ __device__ inline int bins_grid(int64_t n_per) {
+    int g = 1;
+    while (g < kBinGMax && (int64_t)(g + 1) * (g + 1) * kBinPerCell <= n_per) ++g;
+    return g;
+}
+
+struct BinLayout {
+    int G;
+    int64_t sp, si, start, cur, stride;  // word offsets in a trajectory's record
+};
+__host__ __device__ inline BinLayout bins_layout(int64_t n_per) {
+    BinLayout l;
+    l.G = bins_grid(n_per);
+    const int64_t nc = (int64_t)l.G * l.G;
+    l.sp = kBinHdr;
+    l.si = l.sp + 2 * n_per;
+    l.start = l.si + n_per;
+    l.cur = l.start + nc + 1;
+    l.stride = (l.cur + nc + 1) & ~(int64_t)1;
+    return l;
+}
+
+// The cell of coordinate v on an axis of g cells from o, inverse cell size ih
+// (0 when g == 1); NaN and anything outside the box land in an end cell.
+__device__ __forceinline__ int bin_axis(float v, float o, float ih, int g) {
+    const float t = (v - o) * ih;
+    return (int)fminf(fmaxf(t, 0.0f), (float)(g - 1));
+}
+
+// The cell of point c in the grid of the header at W.
+__device__ __forceinline__ int bin_cell(const uint32_t *__restrict__ W, float2 c) {
+    const float *H = (const float *)W;
+    return bin_axis(c.y, H[1], H[5], (int)W[8]) * (int)W[7] + bin_axis(c.x, H[0], H[4], (int)W[7]);
+}
+
+// Binning is four launches: (1) one workgroup per trajectory reduces the box,
+// writes the header and zeroes the cell counts; (2) a thread per point counts
+// its cell (atomics on the workspace); (3) one workgroup per trajectory scans
+// the counts into the cell starts and the scatter cursors; (4) a thread per
+// point takes a slot of its cell.  The order of the points inside a cell
+// depends on the schedule; the search's answer does not ((key, index) is a
+// total order).
+__global__ __launch_bounds__(kBinThreads) void knn_bin_box_kernel(const float2 *__restrict__ src, int n_per,
+                                                                  uint32_t *__restrict__ ws) {
+    constexpr int NW = kBinThreads / 64;
+    __shared__ float red[NW][5];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const BinLayout lay = bins_layout(n_per);
+    const float2 *P = src + (int64_t)b * n_per;
+    uint32_t *W = ws + (int64_t)b * lay.stride;
+    int *cur = (int *)(W + lay.cur);
+
+    float mnx = 3.0e38f, mny = 3.0e38f, mxx = -3.0e38f, mxy = -3.0e38f, mabs = 0.0f;
+    for (int i = tid; i < n_per; i += kBinThreads) {
+        const float2 c = P[i];
+        mnx = fminf(mnx, c.x);
+        mny = fminf(mny, c.y);
+        mxx = fmaxf(mxx, c.x);
+        mxy = fmaxf(mxy, c.y);
+        mabs = fmaxf(mabs, fmaxf(fabsf(c.x), fabsf(c.y)));
+    }
+    mnx = -wave_max_full(-mnx);
+    mny = -wave_max_full(-mny);
+    mxx = wave_max_full(mxx);
+    mxy = wave_max_full(mxy);
+    mabs = wave_max_full(mabs);
+    if (lane == 0) {
+        red[wave][0] = mnx;
+        red[wave][1] = mny;
+        red[wave][2] = mxx;
+        red[wave][3] = mxy;
+        red[wave][4] = mabs;
+    }
+    __syncthreads();
+    float x0 = red[0][0], y0 = red[0][1], x1 = red[0][2], y1 = red[0][3], ma = red[0][4];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) {
+        x0 = fminf(x0, red[w][0]);
+        y0 = fminf(y0, red[w][1]);
+        x1 = fmaxf(x1, red[w][2]);
+        y1 = fmaxf(y1, red[w][3]);
+        ma = fmaxf(ma, red[w][4]);
+    }
+    // eps bounds, on either axis, how far outside its cell's nominal box
+    // [o + c h, o + (c + 1) h] a point can lie plus the rounding of that box's
+    // sides as the search forms them: the cell index carries a relative error
+    // <= 3 2^-24 and h one of 2^-23 (together < 3e-7 of the extent), a side
+    // o + c h an absolute one <= 2^-22 of the largest coordinate.
+    const float ex = x1 - x0, ey = y1 - y0;
+    const float eps = (1.0e-5f * fmaxf(ex, ey) + 2.0e-6f * ma) * kUp;
+    const bool ok = isfinite(ex) && isfinite(ey) && isfinite(eps);
+    int gx = lay.G, gy = lay.G;
+    float hx = ex / gx, hy = ey / gy;
+    float ihx = 1.0f / hx, ihy = 1.0f / hy;
+    if (!ok || !(ex > 0.0f) || !isfinite(ihx)) {
+        gx = 1;
+        hx = ihx = 0.0f;
+    }
+    if (!ok || !(ey > 0.0f) || !isfinite(ihy)) {
+        gy = 1;
+        hy = ihy = 0.0f;
+    }
+    const int nc = gx * gy;
+    if (tid == 0) {
+        float *H = (float *)W;
+        H[0] = x0;
+        H[1] = y0;
+        H[2] = hx;
+        H[3] = hy;
+        H[4] = ihx;
+        H[5] = ihy;
+        H[6] = ok ? eps : 0.0f;
+        W[7] = (uint32_t)gx;
+        W[8] = (uint32_t)gy;
+        W[9] = (uint32_t)n_per;
+    }
+    for (int c = tid; c < nc; c += kBinThreads) cur[c] = 0;
+}
+
+__global__ __launch_bounds__(256) void knn_bin_count_kernel(const float2 *__restrict__ src, int n_per,
+                                                            uint32_t *__restrict__ ws) {
+    const BinLayout lay = bins_layout(n_per);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_per) return;
+    uint32_t *W = ws + (int64_t)blockIdx.y * lay.stride;
+    atomicAdd((int *)(W + lay.cur) + bin_cell(W, src[(int64_t)blockIdx.y * n_per + i]), 1);
+}
+
+// exclusive scan of the counts: a contiguous chunk of cells per thread
+__global__ __launch_bounds__(kBinThreads) void knn_bin_scan_kernel(int n_per, uint32_t *__restrict__ ws) {
+    constexpr int NW = kBinThreads / 64;
+    __shared__ int wsum[NW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const BinLayout lay = bins_layout(n_per);
+    uint32_t *W = ws + (int64_t)blockIdx.x * lay.stride;
+    int *start = (int *)(W + lay.start);
+    int *cur = (int *)(W + lay.cur);
+    const int nc = (int)W[7] * (int)W[8];
+    const int chunk = (nc + kBinThreads - 1) / kBinThreads;
+    const int c0 = min(tid * chunk, nc), c1 = min(c0 + chunk, nc);
+    int sum = 0;
+    for (int c = c0; c < c1; ++c) sum += cur[c];
+    int inc = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += v;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int run = inc - sum;
+    for (int w = 0; w < wave; ++w) run += wsum[w];
+    for (int c = c0; c < c1; ++c) {  // this thread's own cells: the count becomes the cursor
+        const int v = cur[c];
+        start[c] = run;
+        cur[c] = run;
+        run += v;
+    }
+    if (tid == 0) start[nc] = n_per;
+}
+
+__global__ __launch_bounds__(256) void knn_bin_scatter_kernel(const float2 *__restrict__ src, int n_per,
+                                                              uint32_t *__restrict__ ws) {
+    const BinLayout lay = bins_layout(n_per);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_per) return;
+    uint32_t *W = ws + (int64_t)blockIdx.y * lay.stride;
+    const float2 c = src[(int64_t)blockIdx.y * n_per + i];
+    const int pos = atomicAdd((int *)(W + lay.cur) + bin_cell(W, c), 1);
+    if ((unsigned)pos < (unsigned)n_per) {  // always: the counts are these same cells'
+        ((float2 *)(W + lay.sp))[pos] = c;
+        ((int32_t *)(W + lay.si))[pos] = i;
+    }
+}
+
+// One wave per query (QUERY as in knn_kernel), 16 queries per workgroup.
+//  1. the query's cell (cx, cy), clamped into the grid;
+//  2. ring r adds the cells of the block [cx - r, cx + r] x [cy - r, cy + r]
+//     (clipped) not yet scanned: the two end rows, each one contiguous range of
+//     the sorted copy, and the two end cells of the rows between.  Scanned
+//     point number t goes to lane t % 64, which keeps its smallest fp32 key;
+//  3. every unscanned point lies in a cell beyond one of the block's sides that
+//     still has cells beyond it, hence at least D = (the smallest distance from
+//     the query to such a side) - eps away (bin kernel: eps), rounded down;
+//  4. with cnt >= kk points scanned, U = the kk-th smallest lane minimum bounds
+//     the kk-th smallest fp32 key of the whole set from above (min(cnt, 64) >=
+//     kk lanes hold a point), thr = filter_threshold(U) as in knn_kernel;
+//  5. stop when sqrt(thr) < D with the margins below (an unscanned point's
+//     fp32 key is then above thr: it is no candidate), or when the block is
+//     the whole grid;
+//  6. the block's points with fp32 key <= thr, as original indices, are
+//     compacted into the wave's list (block rows are contiguous ranges);
+//  7. knn_finish with the trajectory's global pointer (as knn_tiled_kernel):
+//     the same sorts, overflow select, counters and output.
+// C = {fp32 key <= thr} is exactly the set the full-scan kernels would select
+// with this thr, and any valid U gives the same answer.
+// A header that was not written for this n_src (bins of another set) ends the
+// wave before any indexed read; starts and indices are clamped into range.
+template <bool QUERY>
+__global__ __launch_bounds__(256) void knn_binned_kernel(const float2 *__restrict__ pts,
+                                                         const float2 *__restrict__ qry,
+                                                         const uint32_t *__restrict__ bins, int n_src,
+                                                         int n_q, int k, int32_t *__restrict__ out,
+                                                         int32_t *__restrict__ degenerate,
+                                                         unsigned long long *__restrict__ stats) {
+    typedef KeyTraits<QUERY> KT;
+    typedef typename KT::key_t key_t;
+    __shared__ key_t sKey[4][kCap];
+    __shared__ int sIdx[4][kCap];
+    __shared__ int sSel[4][64];
+
+    const int b = blockIdx.y;
+    const BinLayout lay = bins_layout(n_src);
+    const float2 *P = pts + (int64_t)b * n_src;
+    const uint32_t *W = bins + (int64_t)b * lay.stride;
+    const float *H = (const float *)W;
+    const float2 *SP = (const float2 *)(W + lay.sp);
+    const int32_t *SI = (const int32_t *)(W + lay.si);
+    const int *start = (const int *)(W + lay.start);
+    const float x0 = H[0], y0 = H[1], hx = H[2], hy = H[3], ihx = H[4], ihy = H[5], eps = H[6];
+    const int gx = (int)W[7], gy = (int)W[8];
+    if (gx < 1 || gx > lay.G || gy < 1 || gy > lay.G || (int)W[9] != n_src) return;  // workgroup-uniform
+
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int kk = QUERY ? k : k + 1;
+    const int cpl = (n_src + 63) / 64;
+    const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    auto range_lo = [&](int c) { return min(max(start[c], 0), n_src); };
+    const int q_end = min((int)(blockIdx.x + 1) * kQueriesPerBlock, n_q);
+
+    for (int qi = blockIdx.x * kQueriesPerBlock + wave; qi < q_end; qi += 4) {
+        const float2 q = QUERY ? qry[(int64_t)b * n_q + qi] : P[qi];
+        const int cx = bin_axis(q.x, x0, ihx, gx), cy = bin_axis(q.y, y0, ihy, gy);
+        uint32_t lmin = ~0u, thr = ~0u;
+        int cnt = 0;
+        // points [lo, hi) of the sorted copy, the t-th scanned on lane t % 64
+        auto scan = [&](int lo, int hi) {
+            const int len = hi - lo;
+            for (int o = (lane - cnt) & 63; o < len; o += 64) {
+                const uint32_t f = key_f32(SP[lo + o], q);
+                lmin = f < lmin ? f : lmin;
+            }
+            cnt += max(len, 0);
+        };
+        int cxlo, cxhi, cylo, cyhi;
+        for (int r = 0;; ++r) {
+            cxlo = max(cx - r, 0);
+            cxhi = min(cx + r, gx - 1);
+            cylo = max(cy - r, 0);
+            cyhi = min(cy + r, gy - 1);
+            for (int y = cylo; y <= cyhi; ++y) {
+                const int row = y * gx;
+                if (y == cy - r || y == cy + r) {
+                    scan(range_lo(row + cxlo), range_lo(row + cxhi + 1));
+                } else {
+                    if (cx - r >= 0) scan(range_lo(row + cx - r), range_lo(row + cx - r + 1));
+                    if (cx + r <= gx - 1) scan(range_lo(row + cx + r), range_lo(row + cx + r + 1));
+                }
+            }
+            const bool whole = cxlo == 0 && cxhi == gx - 1 && cylo == 0 && cyhi == gy - 1;
+            if (cnt >= kk) {
+                const uint32_t u = lane_value(wave_sort64(lmin, lane), kk - 1);
+                thr = KT::filter_threshold(u);
+                if (whole) break;
+                float d = 3.0e38f;
+                if (cxlo > 0) d = fminf(d, q.x - (x0 + (float)cxlo * hx));
+                if (cxhi < gx - 1) d = fminf(d, (x0 + (float)(cxhi + 1) * hx) - q.x);
+                if (cylo > 0) d = fminf(d, q.y - (y0 + (float)cylo * hy));
+                if (cyhi < gy - 1) d = fminf(d, (y0 + (float)(cyhi + 1) * hy) - q.y);
+                d = (d - eps) * kDown;
+                // An unscanned point is >= d away, so its fp32 key is >= d^2 (1 -
+                // 2^-22) - 2^-126 (KeyTraits<true>), which exceeds thr when
+                // sqrt(thr) kUp^2 < d and d^2 2^-19 covers the absolute term.
+                // NaN (a non-finite query or thr) compares false: no stop.
+                const float s = sqrtf(__uint_as_float(thr)) * kUp * kUp;
+                if (u != ~0u && d > 1.0e-15f && s < d) break;
+            } else if (whole) {
+                thr = ~0u;  // fewer than kk points in the bins (not this set's): every point a candidate
+                break;
+            }
+        }
+        int m = 0;
+        for (int y = cylo; y <= cyhi; ++y) {
+            const int lo = range_lo(y * gx + cxlo), hi = range_lo(y * gx + cxhi + 1);
+            for (int o0 = 0; o0 < hi - lo; o0 += 64) {
+                const int o = o0 + lane;
+                const bool sel = o < hi - lo && key_f32(SP[lo + o], q) <= thr;
+                const uint64_t sm = __ballot(sel);
+                const int pidx = m + __popcll(sm & below);
+                if (sel && pidx < kCap) sIdx[wave][pidx] = min(max(SI[lo + o], 0), n_src - 1);
+                m += __popcll(sm);
+            }
+        }
+        if (stats && lane == 0) {
+            atomicAdd(&stats[0], (unsigned long long)cnt);
+            if (m > kCap) atomicAdd(&stats[1], 1ull);
+        }
+        knn_finish<QUERY>(P, sKey[wave], sIdx[wave], sSel[wave], m, q, kk, k, qi, b, n_src, n_q, cpl, lane, below,
+                          out, degenerate);
+    }
+}
+
+template <bool QUERY>
+int launch_knn_binned(const float *pts, const float *qry, const void *bins, int64_t batches, int64_t n_src,
+                      int64_t n_q, int k, int32_t *out, int32_t *degenerate, int64_t *stats, hipStream_t st) {
+    const int kk = QUERY ? k : k + 1;
+    // launch_knn's limits
+    if (k < 1 || kk > 64 || n_src < kk || n_src > kTiledMax || n_q < 1 || batches < 1 || batches > 65535 ||
+        n_q > INT32_MAX / 64 || batches * n_src > INT32_MAX)
+        return MMPDE_ERR_INVALID_ARG;
+    dim3 grid(ceil_div(n_q, kQueriesPerBlock), (unsigned)batches);
+    hipLaunchKernelGGL(knn_binned_kernel<QUERY>, grid, dim3(256), 0, st, (const float2 *)pts, (const float2 *)qry,
+                       (const uint32_t *)bins, (int)n_src, (int)n_q, k, out, degenerate,
+                       (unsigned long long *)stats);
+    MMPDE_RET_LAUNCH();
+    return MMPDE_OK;
+}
+
 }  // namespace
 
 extern "C" int mmpde_knn_graph(const float *pos, int64_t batches, int64_t n_per, int k,
@@ -1439,6 +1780,51 @@ extern "C" int mmpde_knn_query(const float *src, const float *qry, int64_t batch
                                mmpde_stream_t stream) {
     MMPDE_REQUIRE(src && qry && idx_out);
     return launch_knn<true>(src, qry, batches, n_src, n_qry, k, idx_out, ties, as_stream(stream));
+}
+
+extern "C" int mmpde_knn_bins_grid(int64_t n_per) {
+    return n_per < 1 || n_per > kTiledMax ? 0 : bins_grid(n_per);
+}
+
+extern "C" int64_t mmpde_knn_bins_bytes(int64_t batches, int64_t n_per) {
+    if (batches < 1 || batches > 65535 || n_per < 1 || n_per > kTiledMax) return 0;
+    return batches * bins_layout(n_per).stride * (int64_t)sizeof(uint32_t);
+}
+
+extern "C" int mmpde_knn_bin(const float *src, int64_t batches, int64_t n_per, void *bins, int64_t bins_bytes,
+                             mmpde_stream_t stream) {
+    MMPDE_REQUIRE(src && bins && batches >= 1 && batches <= 65535 && n_per >= 1 && n_per <= kTiledMax &&
+                  batches * n_per <= INT32_MAX && ((uintptr_t)bins & 7) == 0 &&
+                  bins_bytes >= mmpde_knn_bins_bytes(batches, n_per));
+    hipStream_t st = as_stream(stream);
+    const float2 *p = (const float2 *)src;
+    uint32_t *w = (uint32_t *)bins;
+    const dim3 per_traj((unsigned)batches), per_point(ceil_div(n_per, 256), (unsigned)batches);
+    hipLaunchKernelGGL(knn_bin_box_kernel, per_traj, dim3(kBinThreads), 0, st, p, (int)n_per, w);
+    MMPDE_RET_LAUNCH();
+    hipLaunchKernelGGL(knn_bin_count_kernel, per_point, dim3(256), 0, st, p, (int)n_per, w);
+    MMPDE_RET_LAUNCH();
+    hipLaunchKernelGGL(knn_bin_scan_kernel, per_traj, dim3(kBinThreads), 0, st, (int)n_per, w);
+    MMPDE_RET_LAUNCH();
+    hipLaunchKernelGGL(knn_bin_scatter_kernel, per_point, dim3(256), 0, st, p, (int)n_per, w);
+    MMPDE_RET_LAUNCH();
+    return MMPDE_OK;
+}
+
+extern "C" int mmpde_knn_graph_binned(const float *pos, const void *bins, int64_t batches, int64_t n_per, int k,
+                                      int32_t *nbr_out, int32_t *degenerate, int64_t *stats,
+                                      mmpde_stream_t stream) {
+    MMPDE_REQUIRE(pos && bins && nbr_out && ((uintptr_t)bins & 7) == 0);
+    return launch_knn_binned<false>(pos, nullptr, bins, batches, n_per, n_per, k, nbr_out, degenerate, stats,
+                                    as_stream(stream));
+}
+
+extern "C" int mmpde_knn_query_binned(const float *src, const void *bins, const float *qry, int64_t batches,
+                                      int64_t n_src, int64_t n_qry, int k, int32_t *idx_out, int32_t *ties,
+                                      int64_t *stats, mmpde_stream_t stream) {
+    MMPDE_REQUIRE(src && bins && qry && idx_out && ((uintptr_t)bins & 7) == 0);
+    return launch_knn_binned<true>(src, qry, bins, batches, n_src, n_qry, k, idx_out, ties, stats,
+                                   as_stream(stream));
 }
 
 extern "C" int mmpde_radius_graph(const float *pos, int64_t batches, int64_t n_per, float r,

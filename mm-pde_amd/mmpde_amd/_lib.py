@@ -13,7 +13,7 @@ import os
 import torch
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmmpde_hip.so")
-ABI_VERSION = 12200
+ABI_VERSION = 12300
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_ELU = 0, 1, 2, 3
 PAD_ZEROS, PAD_CIRCULAR = 0, 1
@@ -125,6 +125,11 @@ _SIGS = {
     "mmpde_knn_graph_cand": (_I, [_P, _P, _P, _F, _I64, _I64, _I, _P, _P, _P, _P, _P]),
     "mmpde_knn_query_cand": (_I, [_P, _P, _P, _P, _P, _F, _I64, _I64, _I, _P, _P, _P, _P, _P]),
     "mmpde_knn_query": (_I, [_P, _P, _I64, _I64, _I64, _I, _P, _P, _P]),
+    "mmpde_knn_bins_grid": (_I, [_I64]),
+    "mmpde_knn_bins_bytes": (_I64, [_I64, _I64]),
+    "mmpde_knn_bin": (_I, [_P, _I64, _I64, _P, _I64, _P]),
+    "mmpde_knn_graph_binned": (_I, [_P, _P, _I64, _I64, _I, _P, _P, _P, _P]),
+    "mmpde_knn_query_binned": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, _P, _P, _P, _P]),
     "mmpde_edge_index_from_nbr": (_I, [_P, _I64, _I, _P, _P]),
     "mmpde_linear_skinny": (_I, [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _I, _P, _I64, _P]),
     "mmpde_linear_skinny_workspace_bytes": (_I64, [_I64, _I64, _I64]),

@@ -38,6 +38,10 @@ class GraphCreator_FS_2D(nn.Module):  # noqa: N801 - reference name
         assert isinstance(self.n, int)
         assert isinstance(self.tw, int)
         self._fixed_graph_cache = {}
+        # "full" or "binned" (ops.knn_graph_nbr / ops.knn_query): how create_graph's
+        # moved-mesh graph and the kNN-30 queries of interpolate / interpolate_pred
+        # search; the same tables either way
+        self.knn_method = "full"
 
     # ------------------------------------------------------------------ grids
     def _is_array(self):
@@ -145,7 +149,7 @@ class GraphCreator_FS_2D(nn.Module):  # noqa: N801 - reference name
         nu = u.shape[0]
         src = torch.cat((init_x, init_y), -1).reshape(-1, 2)
         qry = torch.cat((x, y), -1).reshape(-1, 2)
-        idx = ops.knn_query(src, qry, nu, 30)
+        idx = ops.knn_query(src, qry, nu, 30, method=self.knn_method)
         if itp_model.training:
             return self._interpolate_autograd(itp_model, u, src, qry, idx, nu, mode)
         return ops.itp_interp(src, u.reshape(-1), qry, idx, nu, itp_model.packed(mode))
@@ -235,7 +239,7 @@ class GraphCreator_FS_2D(nn.Module):  # noqa: N801 - reference name
         elif mesh_model is None:
             nbr = self.fixed_graph_nbr(grid, B)
         else:
-            nbr = ops.knn_graph_nbr(mesh, B, self.n)
+            nbr = ops.knn_graph_nbr(mesh, B, self.n, method=self.knn_method)
         return self._graph(u_nodes.contiguous(), mesh.contiguous(), t_nodes, y_nodes, nbr, B, n,
                            deg)
 
@@ -258,7 +262,7 @@ class GraphCreator_FS_2D(nn.Module):  # noqa: N801 - reference name
             res = itp_model.res_cut(data.reshape(-1, n)).reshape(-1)
             n_src = n
         src = graph.pos[:, 1:3].contiguous()
-        idx = ops.knn_query(src, qry, nu, 30)
+        idx = ops.knn_query(src, qry, nu, 30, method=self.knn_method)
         if itp_model.training:
             out = self._interpolate_autograd(itp_model, pred, src, qry, idx, nu, "2",
                                              addend=res)

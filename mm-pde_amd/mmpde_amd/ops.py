@@ -32,21 +32,88 @@ def _knn_points_check(n_per: int, k: int, what: str):
         raise ValueError(f"{what}: k = {k}; the HIP kNN kernels take k <= 63")
 
 
-def knn_graph_nbr(pos: torch.Tensor, batches: int, k: int, count_degenerate: bool = False):
+# Trajectories of at least this many points are searched through cell bins by
+# the rollout when no candidate table exists (knn_bins; csrc/knn.hip
+# knn_binned_kernel): the binned search beat the full one at every measured
+# size from 4225 points up (profiles/knn_binned_times.txt).
+KNN_BINNED_MIN_POINTS = 4097
+KNN_METHODS = ("full", "binned")
+
+
+def knn_bins_grid(n_per: int) -> int:
+    """Cells per axis of the grid knn_bins lays over a trajectory of n_per
+    points (mmpde_knn_bins_grid; host arithmetic)."""
+    return int(L.lib().mmpde_knn_bins_grid(int(n_per)))
+
+
+def knn_bins(src: torch.Tensor, batches: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Cell bins of src [batches * n_per, 2] for knn_graph_nbr / knn_query with
+    method="binned": every trajectory's points sorted into a uniform grid over
+    its own bounding box (mmpde_knn_bin).  One binning serves any number of
+    searches of the same points.  out: a uint8 workspace to reuse (at least
+    mmpde_knn_bins_bytes(batches, n_per) bytes), else allocated."""
+    L.require_device(src)
+    src = L.f32c(src).reshape(-1, 2)
+    n = src.shape[0]
+    if batches < 1 or n % batches or n == 0:
+        raise ValueError("src rows must split into equal batch segments")
+    n_per = n // batches
+    _knn_points_check(n_per, 1, "knn_bins")
+    need = L.lib().mmpde_knn_bins_bytes(batches, n_per)
+    if out is None:
+        out = torch.empty((need,), dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < need:
+        raise ValueError(f"knn_bins: out must be a contiguous uint8 device tensor of >= {need} bytes")
+    L.check(L.lib().mmpde_knn_bin(L.ptr(src), batches, n_per, L.ptr(out), out.numel(),
+                                  L.stream(src.device)), "mmpde_knn_bin")
+    return out
+
+
+def _knn_method(method, bins, stats, src, batches, n_per):
+    """Validated (bins, stats) of a search with `method`; bins built when absent."""
+    if method not in KNN_METHODS:
+        raise ValueError(f"knn method {method!r}; one of {KNN_METHODS}")
+    if method == "full":
+        if bins is not None or stats is not None:
+            raise ValueError('bins / stats belong to method="binned"')
+        return None, None
+    if stats is not None and (stats.dtype != torch.int64 or stats.numel() < 2 or not stats.is_cuda
+                              or not stats.is_contiguous()):
+        raise ValueError("stats must be an int64[2] device counter")
+    if bins is None:
+        bins = knn_bins(src, batches)
+    elif (bins.dtype != torch.uint8 or not bins.is_cuda or not bins.is_contiguous()
+          or bins.numel() < L.lib().mmpde_knn_bins_bytes(batches, n_per)):
+        raise ValueError("bins must come from knn_bins of the same source points")
+    return bins, stats
+
+
+def knn_graph_nbr(pos: torch.Tensor, batches: int, k: int, count_degenerate: bool = False,
+                  method: str = "full", bins: torch.Tensor | None = None,
+                  stats: torch.Tensor | None = None):
     """torch_cluster.knn_graph(pos, k, batch, loop=False) for `batches` equal
     contiguous segments (reference data_creator_2d.py:260, dmm_model.py:228).
     Returns nbr [n, k] int32 (global source indices, (d2, index) order)
-    [, degenerate count tensor]."""
+    [, degenerate count tensor].  method "binned": the same table from the cell
+    bins of pos (bins = knn_bins(pos, batches), built here when None); stats:
+    optional int64[2] device counter, += (points examined, queries whose
+    candidate list overflowed)."""
     L.require_device(pos)
     pos = L.f32c(pos).reshape(-1, 2)
     n = pos.shape[0]
     if n % batches:
         raise ValueError("pos rows must split into equal batch segments")
     _knn_points_check(n // batches, k, "knn_graph")
+    bins, stats = _knn_method(method, bins, stats, pos, batches, n // batches)
     nbr = torch.empty((n, k), dtype=torch.int32, device=pos.device)
     deg = torch.zeros((1,), dtype=torch.int32, device=pos.device) if count_degenerate else None
-    L.check(L.lib().mmpde_knn_graph(L.ptr(pos), batches, n // batches, k, L.ptr(nbr),
-                                    L.ptr(deg), L.stream(pos.device)), "mmpde_knn_graph")
+    if method == "binned":
+        L.check(L.lib().mmpde_knn_graph_binned(L.ptr(pos), L.ptr(bins), batches, n // batches, k, L.ptr(nbr),
+                                               L.ptr(deg), L.ptr(stats), L.stream(pos.device)),
+                "mmpde_knn_graph_binned")
+    else:
+        L.check(L.lib().mmpde_knn_graph(L.ptr(pos), batches, n // batches, k, L.ptr(nbr),
+                                        L.ptr(deg), L.stream(pos.device)), "mmpde_knn_graph")
     return (nbr, deg) if count_degenerate else nbr
 
 
@@ -337,20 +404,29 @@ def _ties(ties):
 
 
 def knn_query(src: torch.Tensor, qry: torch.Tensor, batches: int, k: int,
-              ties: torch.Tensor | None = None) -> torch.Tensor:
+              ties: torch.Tensor | None = None, method: str = "full",
+              bins: torch.Tensor | None = None, stats: torch.Tensor | None = None) -> torch.Tensor:
     """Per-trajectory sklearn NearestNeighbors(k).fit(src_b).kneighbors(qry_b):
     LOCAL indices int32 [batches * n_qry, k], fp64-distance order
     (reference data_creator_2d.py:66-78).  ties: optional int32 [1] device
     counter, += the queries with an exact fp64 distance tie among their first
-    k (or at rank k): where sklearn's order is its KD-tree's, parity unpinned."""
+    k (or at rank k): where sklearn's order is its KD-tree's, parity unpinned.
+    method "binned": the same table from the cell bins of src (bins =
+    knn_bins(src, batches), built here when None); stats as for knn_graph_nbr."""
     L.require_device(src, qry)
     src = L.f32c(src).reshape(-1, 2)
     qry = L.f32c(qry).reshape(-1, 2)
     ns, nq = src.shape[0] // batches, qry.shape[0] // batches
     _knn_points_check(ns, k, "knn_query")
+    bins, stats = _knn_method(method, bins, stats, src, batches, ns)
     idx = torch.empty((batches * nq, k), dtype=torch.int32, device=src.device)
-    L.check(L.lib().mmpde_knn_query(L.ptr(src), L.ptr(qry), batches, ns, nq, k, L.ptr(idx),
-                                    L.ptr(_ties(ties)), L.stream(src.device)), "mmpde_knn_query")
+    if method == "binned":
+        L.check(L.lib().mmpde_knn_query_binned(L.ptr(src), L.ptr(bins), L.ptr(qry), batches, ns, nq, k,
+                                               L.ptr(idx), L.ptr(_ties(ties)), L.ptr(stats),
+                                               L.stream(src.device)), "mmpde_knn_query_binned")
+    else:
+        L.check(L.lib().mmpde_knn_query(L.ptr(src), L.ptr(qry), batches, ns, nq, k, L.ptr(idx),
+                                        L.ptr(_ties(ties)), L.stream(src.device)), "mmpde_knn_query")
     return idx
 
 

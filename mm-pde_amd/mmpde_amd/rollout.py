@@ -117,6 +117,16 @@ class MMPDERollout:
             # an earlier step (ops.KnnTablePolicy: the cost model, no sync)
             self.knn_policy = ops.KnnTablePolicy(
                 self.device, batches, N, ("graph", "query") + (("query1",) if kind == "burgers" else ()))
+            # Without a candidate table (N > 4096) the per-step searches go
+            # through cell bins of the moved mesh instead of scanning the whole
+            # trajectory (ops.knn_bins; csrc/knn.hip knn_binned_kernel): the
+            # same tables.  Settable before the first step; with it on, the
+            # tables above are not consulted.
+            self.knn_binned = self.knn_cand is None and N >= ops.KNN_BINNED_MIN_POINTS
+            self.knn_bins = None     # the moved mesh's bins, rebuilt every step (main1)
+            self.knn_bins_1 = None   # burgers mode '1': the fixed grid's bins, built once
+            if self.knn_binned:
+                self._ensure_bins()
             # the fixed-grid model depends on u only: it runs on a side stream,
             # with its own workspace, beside the moving-mesh chain
             self.ws_gnn_u = torch.empty_like(self.ws_gnn)
@@ -163,6 +173,7 @@ class MMPDERollout:
     # of the C-ABI's; each stage runs on the caller's current stream):
     #   side   model(u) on the fixed grid                       needs u
     #   main1  DMM mesh, per-trajectory displacement record     needs u
+    #          (knn_binned: the moved mesh's cell bins instead)
     #   side2  kNN-30 query onto the fixed grid, res_cut(u)     needs main1
     #   main2  moved-mesh kNN-35 graph (Burgers: u onto the moved mesh), model_b
     #   final  interpolation + res_cut + model(u) in one kernel  needs all
@@ -170,9 +181,24 @@ class MMPDERollout:
         nodes_u = self._nodes(u_flat, self.grid_rep, self.nbr_u, step_idx)
         self.model(nodes_u, out=self.out_u, workspace=self.ws_gnn_u, trace=self._trace())
 
+    def _ensure_bins(self):
+        if self.knn_bins is None:
+            nb = L.lib().mmpde_knn_bins_bytes(self.B, self.N)
+            self.knn_bins = torch.empty((nb,), dtype=torch.uint8, device=self.device)
+        if self.kind == "burgers" and self.knn_bins_1 is None:
+            self.knn_bins_1 = ops.knn_bins(self.grid_rep, self.B)
+
     def _st_main1(self, u):
         B = self.B
         self.dmm.mesh(u, self.xi, out=self.mesh, workspace=self.ws_dmm, head_cache=self.dmm_cache)
+        if self.knn_binned:
+            # one binning of the moved mesh for the kNN-30 query (side2) and the graph (main2)
+            self._ensure_bins()
+            ops.knn_bins(self.mesh, B, out=self.knn_bins)
+            self._use_g = self._use_q = False
+            self._knn_used = {"graph": False, "query": False}
+            self._cells = None
+            return
         pol = self.knn_policy
         self._use_g, self._use_q = pol.use_table("graph"), pol.use_table("query")
         self._knn_used = {"graph": self._use_g, "query": self._use_q}
@@ -182,7 +208,10 @@ class MMPDERollout:
     def _st_side2(self, u):
         B, N = self.B, self.N
         pol, cells, mesh = self.knn_policy, self._cells, self.mesh
-        if self._use_q:
+        if self.knn_binned:
+            idx2 = ops.knn_query(mesh, self.grid_rep, B, 30, ties=self.knn_ties, method="binned",
+                                 bins=self.knn_bins)
+        elif self._use_q:
             idx2 = ops.knn_query_moved(mesh, self.grid_rep, self.xi, self.knn_cand_q, B, 30,
                                        self.knn_scratch_q, ref=self.grid, cells=cells,
                                        skip_above=self.knn_skip_q, ties=self.knn_ties)
@@ -199,7 +228,9 @@ class MMPDERollout:
     def _st_main2(self, u_flat, step_idx):
         B = self.B
         pol, cells, mesh = self.knn_policy, self._cells, self.mesh
-        if self._use_g:
+        if self.knn_binned:
+            nbr_m = ops.knn_graph_nbr(mesh, B, self.gc.n, method="binned", bins=self.knn_bins)
+        elif self._use_g:
             nbr_m = ops.knn_graph_moved(mesh, self.xi, self.knn_cand, B, self.gc.n, self.knn_scratch,
                                         cells=cells, skip_above=self.knn_skip)
             if cells is not None:
@@ -208,8 +239,11 @@ class MMPDERollout:
             nbr_m = ops.knn_graph_nbr(mesh, B, self.gc.n)
         self.nbr_m = nbr_m
         if self.kind == "burgers":
-            self._knn_used["query1"] = pol.use_table("query1")
-            if self._knn_used["query1"]:
+            self._knn_used["query1"] = not self.knn_binned and pol.use_table("query1")
+            if self.knn_binned:
+                idx1 = ops.knn_query(self.grid_rep, mesh, B, 30, ties=self.knn_ties, method="binned",
+                                     bins=self.knn_bins_1)
+            elif self._knn_used["query1"]:
                 cells1 = ops.knn_moved_cells(self.grid_rep, self.grid, B, out=self.knn_cells_1)
                 idx1 = ops.knn_query_moved(self.grid_rep, mesh, self.grid, self.knn_cand_1, B, 30,
                                            self.knn_scratch_1, ref=self.xi, cells=cells1,
@@ -361,9 +395,12 @@ class MMPDERollout:
         return tuple(s)
 
     def knn_modes(self):
-        """Per kNN search of the step: 'table', 'full' or 'probe' (ops.KnnTablePolicy)."""
+        """Per kNN search of the step: 'binned' (knn_binned), else 'table', 'full'
+        or 'probe' (ops.KnnTablePolicy)."""
         if not self.moving_mesh:
             return {}
+        if self.knn_binned:
+            return {r: "binned" for r in self.knn_policy.state}
         return {r: self.knn_policy.mode(r) for r in self.knn_policy.state}
 
     def knn_query_ties(self) -> int:
