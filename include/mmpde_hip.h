@@ -202,6 +202,23 @@ int mmpde_radius_graph(const float *pos, int64_t batches, int64_t n_per, float r
                        int max_num_neighbors, int32_t *nbr_out, int32_t *degree_out,
                        mmpde_stream_t stream);
 
+/* mmpde_radius_graph (data_creator_2d.py:257-258) through the cell bins of pos
+ * (bins = mmpde_knn_bin of the same points): the same predicate on the same
+ * floats, nbr_out and degree_out bit for bit those of mmpde_radius_graph.  A
+ * query examines only the cells its radius can reach; when those hold more
+ * than a set share of the trajectory it runs the index-order scan of
+ * mmpde_radius_graph instead (a radius that covers much of the domain, e.g.
+ * the reference's default neighbors = 35, fills a row within a few dozen
+ * points).  Refused with MMPDE_ERR_INVALID_ARG before any launch: a null pos,
+ * bins, nbr_out or degree_out, bins not 8-byte aligned, n_per outside
+ * 1..65536, max_num_neighbors outside 1..63 (the selection keeps one index per
+ * lane of a wave), r <= 0 or NaN, batches outside 1..65535.  stats: optional
+ * device int64[2], += (points examined, queries that took the index-order
+ * scan). */
+int mmpde_radius_graph_binned(const float *pos, const void *bins, int64_t batches, int64_t n_per,
+                              float r, int max_num_neighbors, int32_t *nbr_out, int32_t *degree_out,
+                              int64_t *stats, mmpde_stream_t stream);
+
 /* PyG edge_index (int64 [2, n*k]) from a target-major neighbour table.
  * Row 0 = source (nbr), row 1 = target. (data_creator_2d.py:260-262) */
 int mmpde_edge_index_from_nbr(const int32_t *nbr, int64_t n, int k, int64_t *edge_index,

@@ -1236,21 +1236,27 @@ __global__ __launch_bounds__(256) void knn_cand_kernel(const float2 *__restrict_
 // dropped.  One wave per query, 64 candidates per step, ballot order = index
 // order; stops once w points were taken.  nbr [n, w] global sources ascending,
 // padded with -1; deg [n] = entries kept (w - 1 or w).
-__global__ __launch_bounds__(256) void radius_kernel(const float2 *__restrict__ pts, int n_per,
-                                                     float r2, int w, int32_t *__restrict__ nbr,
-                                                     int32_t *__restrict__ deg) {
-    const int b = blockIdx.y;
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (q >= n_per) return;  // wave-uniform: no barrier below
-    const float2 *P = pts + (int64_t)b * n_per;
-    const float2 qp = P[q];
-    const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    int32_t *row = nbr + ((int64_t)b * n_per + q) * w;
-    int taken = 0, kept = 0;
-    for (int j0 = 0; j0 < n_per && taken < w; j0 += 64) {
+// The hit predicate of both radius kernels, on the same floats: fp32 squared
+// distance (the graph key) strictly below r2, compared as raw bits (NaN and
+// infinite keys order above every finite r2: no hit).
+__device__ __forceinline__ bool radius_hit(float2 p, float2 q, float r2) {
+    return key_f32(p, q) < __float_as_uint(r2);
+}
+
+// torch_cluster squares r on the host in double and hands the kernel a float
+inline float radius_r2(float r) { return (float)((double)r * (double)r); }
+
+// The index-order scan of one query (local index q, point qp) over its
+// trajectory's points P, by one wave: the row and its degree as described
+// above.  Returns the number of points examined (whole steps of 64, clipped to
+// n_per).
+__device__ __forceinline__ int radius_scan(const float2 *__restrict__ P, int n_per, float2 qp, int q, int b,
+                                           float r2, int w, int32_t *__restrict__ row,
+                                           int32_t *__restrict__ deg_out, int lane, uint64_t below) {
+    int taken = 0, kept = 0, j0 = 0;
+    for (; j0 < n_per && taken < w; j0 += 64) {
         const int j = j0 + lane;
-        const bool hit = j < n_per && key_f32(P[j], qp) < __float_as_uint(r2);
+        const bool hit = j < n_per && radius_hit(P[j], qp, r2);
         const uint64_t hm = __ballot(hit);
         const bool take = hit && taken + __popcll(hm & below) < w;
         const uint64_t tm = __ballot(take);
@@ -1260,7 +1266,21 @@ __global__ __launch_bounds__(256) void radius_kernel(const float2 *__restrict__ 
         kept += __popcll(km);
     }
     for (int e = kept + lane; e < w; e += 64) row[e] = -1;
-    if (lane == 0) deg[(int64_t)b * n_per + q] = kept;
+    if (lane == 0) *deg_out = kept;
+    return min(j0, n_per);
+}
+
+__global__ __launch_bounds__(256) void radius_kernel(const float2 *__restrict__ pts, int n_per,
+                                                     float r2, int w, int32_t *__restrict__ nbr,
+                                                     int32_t *__restrict__ deg) {
+    const int b = blockIdx.y;
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (q >= n_per) return;  // wave-uniform: no barrier below
+    const float2 *P = pts + (int64_t)b * n_per;
+    const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const int64_t g = (int64_t)b * n_per + q;
+    radius_scan(P, n_per, P[q], q, b, r2, w, nbr + g * w, deg + g, lane, below);
 }
 
 __global__ void edge_index_kernel(const int32_t *__restrict__ nbr, int64_t n, int k,
@@ -1613,6 +1633,159 @@ int launch_knn_binned(const float *pts, const float *qry, const void *bins, int6
     return MMPDE_OK;
 }
 
+
+// radius_kernel's table from the cell bins of pos (mmpde_knn_bin): the cost of
+// a query follows the number of points near it, not the trajectory's size.
+// One wave per query, four per workgroup.
+//  1. Reach.  A hit has fp32 key f < r2, and f >= d^2 (1 - 2^-22) - 2^-126 for
+//     the exact distance d of the two fp32 points (KeyTraits<true>), so
+//     d < R0 = sqrtf(r2) kUp^2 + 1e-18 (sqrtf's 2^-24 and the 2^-63 of the
+//     absolute term are inside the kUp = 1 + 2^-20 factors and the 1e-18).
+//     R = (R0 + eps) kUp with the header's eps: eps >= 2^-19 of the largest
+//     coordinate and R 2^-20 cover the rounding of q -+ R (<= 2^-24 (|q| + R)),
+//     so fl(q.x - R) <= p.x <= fl(q.x + R) for every hit p, and likewise in y;
+//     eps also is how far outside its cell's nominal box a point can lie.
+//  2. Block.  bin_axis is monotone in the coordinate (a rounded difference, a
+//     product with ih >= 0, a clamp, a truncation) and is the function that
+//     binned p, so p's cell lies in [bin_axis(q.x - R), bin_axis(q.x + R)] x
+//     [bin_axis(q.y - R), bin_axis(q.y + R)]: every hit is in the block.  Each
+//     block row is one contiguous range of the sorted copy.
+//  3. Fallback.  A block of more than kRadiusScanNum / kRadiusScanDen of the
+//     grid's cells (known without a load: a radius that covers much of the
+//     domain), or whose point count, summed from the cell starts before any
+//     point is read, exceeds that share of n_per (a heavy cell), runs
+//     radius_scan on the original points: its early exit at w hits makes it
+//     the cheaper path there.  The share is the measured break-even
+//     (profiles/radius_times.txt: the scan and the binned path cost the same
+//     at blocks of about 14 % of the trajectory, from 9216 to 65536 points).
+//  4. Otherwise the block's hits arrive in bin order.  `best` holds the 64
+//     smallest original indices seen so far, ascending in lane order (~0u:
+//     none).  Hits below the current w-th smallest are compacted into a
+//     128-entry LDS list; each full batch of 64 is sorted descending and
+//     merged: min(best, batch) per lane is bitonic and holds the 64 smallest
+//     of the 128, one bitonic merge sorts it.  Any number of hits gives the w
+//     smallest indices exactly; nothing is truncated.
+//  5. Lanes < w of best are the first w hits in index order; the self loop is
+//     dropped and the row padded as radius_scan does.
+// A header that was not written for this n_per ends the wave before any
+// indexed read; starts and indices are clamped into range.
+constexpr int kRadiusScanNum = 1, kRadiusScanDen = 8;
+
+__device__ __forceinline__ uint32_t radius_merge64(uint32_t best, uint32_t v, int lane) {
+    const uint32_t desc = ~wave_sort64(~v, lane);
+    uint32_t m = min(best, desc);
+#pragma unroll
+    for (int s = 5; s >= 0; --s) {  // (a counted loop: xor_lane needs j to fold to a constant)
+        const int j = 1 << s;
+        const uint32_t o = xor_lane(m, j, lane);
+        m = (lane & j) == 0 ? min(m, o) : max(m, o);
+    }
+    return m;
+}
+
+__global__ __launch_bounds__(256) void radius_binned_kernel(const float2 *__restrict__ pts,
+                                                            const uint32_t *__restrict__ bins,
+                                                            const BinLayout lay, int n_per, float r2, int w,
+                                                            int32_t *__restrict__ nbr,
+                                                            int32_t *__restrict__ deg,
+                                                            unsigned long long *__restrict__ stats) {
+    __shared__ uint32_t sHit[4][128];
+    const int b = blockIdx.y;
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int qi = blockIdx.x * 4 + wave;
+    if (qi >= n_per) return;  // wave-uniform: no workgroup barrier below
+    // lay = bins_layout(n_per) from the host: its grid-size loop would run in every wave
+    const float2 *P = pts + (int64_t)b * n_per;
+    const float2 q = P[qi];
+    const uint32_t *W = bins + (int64_t)b * lay.stride;
+    const float2 *SP = (const float2 *)(W + lay.sp);
+    const int32_t *SI = (const int32_t *)(W + lay.si);
+    const int *start = (const int *)(W + lay.start);
+    // The header's words in four independent 8-byte loads beside the query's
+    // point, and the block (arithmetic only, harmless on a foreign header)
+    // before the branch on the header: one memory round trip ahead of the
+    // fallback's scan, not three.
+    const uint2 *H2 = (const uint2 *)W;
+    const uint2 h0 = H2[0], h2 = H2[2], h3 = H2[3], h4 = H2[4];
+    const float x0 = __uint_as_float(h0.x), y0 = __uint_as_float(h0.y);
+    const float ihx = __uint_as_float(h2.x), ihy = __uint_as_float(h2.y), eps = __uint_as_float(h3.x);
+    const int gx = (int)h3.y, gy = (int)h4.x;
+    const float R = (sqrtf(r2) * kUp * kUp + 1.0e-18f + eps) * kUp;
+    const int cxlo = bin_axis(q.x - R, x0, ihx, gx), cxhi = bin_axis(q.x + R, x0, ihx, gx);
+    const int cylo = bin_axis(q.y - R, y0, ihy, gy), cyhi = bin_axis(q.y + R, y0, ihy, gy);
+    // (bin_axis is monotone, so cxlo <= cxhi and cylo <= cyhi; a non-finite query hits nothing either way)
+    const int ncell = (cxhi - cxlo + 1) * (cyhi - cylo + 1);
+    // ncell < 1 never holds for a grid this n_per's binning wrote
+    if ((gx < 1) | (gx > lay.G) | (gy < 1) | (gy > lay.G) | ((int)h4.y != n_per) | (ncell < 1)) return;
+    const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    auto range_lo = [&](int c) { return min(max(start[c], 0), n_per); };
+    const int64_t g = (int64_t)b * n_per + qi;
+    int32_t *row = nbr + g * w;
+
+    bool scan = ncell * kRadiusScanDen > gx * gy * kRadiusScanNum;
+    int total = 0;
+    if (!scan) {
+        for (int y = cylo + lane; y <= cyhi; y += 64)
+            total += max(range_lo(y * gx + cxhi + 1) - range_lo(y * gx + cxlo), 0);
+#pragma unroll
+        for (int j = 1; j <= 32; j <<= 1) total += (int)xor_lane((uint32_t)total, j, lane);
+        scan = (int64_t)total * kRadiusScanDen > (int64_t)n_per * kRadiusScanNum;
+    }
+    if (scan) {
+        const int seen = radius_scan(P, n_per, q, qi, b, r2, w, row, deg + g, lane, below);
+        if (stats && lane == 0) {
+            atomicAdd(&stats[0], (unsigned long long)seen);
+            atomicAdd(&stats[1], 1ull);
+        }
+        return;
+    }
+
+    uint32_t best = ~0u;
+    uint32_t *list = sHit[wave];
+    int m = 0;
+    for (int y = cylo; y <= cyhi; ++y) {
+        const int lo = range_lo(y * gx + cxlo), len = range_lo(y * gx + cxhi + 1) - lo;
+        for (int o0 = 0; o0 < len; o0 += 64) {
+            const int o = o0 + lane;
+            uint32_t idx = ~0u;
+            bool hit = false;
+            if (o < len) {
+                idx = (uint32_t)min(max(SI[lo + o], 0), n_per - 1);
+                hit = radius_hit(SP[lo + o], q, r2);
+            }
+            // lane w - 1 of best: the w-th smallest so far (~0u: fewer than w)
+            hit = hit && idx < lane_value(best, w - 1);
+            const uint64_t hm = __ballot(hit);
+            if (hit) list[m + __popcll(hm & below)] = idx;  // m < 64: at most 127
+            m += __popcll(hm);
+            if (m >= 64) {
+                wave_lds_sync();
+                const uint32_t v = list[lane];
+                const uint32_t rest = lane + 64 < m ? list[lane + 64] : ~0u;
+                best = radius_merge64(best, v, lane);
+                wave_lds_sync();
+                list[lane] = rest;
+                m -= 64;
+            }
+        }
+    }
+    if (m > 0) {
+        wave_lds_sync();
+        best = radius_merge64(best, lane < m ? list[lane] : ~0u, lane);
+    }
+    const bool take = lane < w && best != ~0u;
+    const bool keep = take && (int)best != qi;  // self loop dropped
+    const uint64_t km = __ballot(keep);
+    const int kept = __popcll(km);
+    if (keep) row[__popcll(km & below)] = b * n_per + (int)best;
+    for (int e = kept + lane; e < w; e += 64) row[e] = -1;
+    if (lane == 0) {
+        deg[g] = kept;
+        if (stats) atomicAdd(&stats[0], (unsigned long long)total);
+    }
+}
+
 }  // namespace
 
 extern "C" int mmpde_knn_graph(const float *pos, int64_t batches, int64_t n_per, int k,
@@ -1833,11 +2006,24 @@ extern "C" int mmpde_radius_graph(const float *pos, int64_t batches, int64_t n_p
     MMPDE_REQUIRE(pos && nbr_out && degree_out);
     MMPDE_REQUIRE(batches > 0 && batches <= 65535 && n_per > 0 && n_per <= INT32_MAX &&
                   batches * n_per <= INT32_MAX && max_num_neighbors > 0 && r > 0.0f);
-    // torch_cluster squares r on the host in double and hands the kernel a float
-    const float r2 = (float)((double)r * (double)r);
     hipLaunchKernelGGL(radius_kernel, dim3((unsigned)ceil_div(n_per, 4), (unsigned)batches),
-                       dim3(256), 0, as_stream(stream), (const float2 *)pos, (int)n_per, r2,
+                       dim3(256), 0, as_stream(stream), (const float2 *)pos, (int)n_per, radius_r2(r),
                        max_num_neighbors + 1, nbr_out, degree_out);
+    MMPDE_RET_LAUNCH();
+    return MMPDE_OK;
+}
+
+extern "C" int mmpde_radius_graph_binned(const float *pos, const void *bins, int64_t batches, int64_t n_per,
+                                         float r, int max_num_neighbors, int32_t *nbr_out,
+                                         int32_t *degree_out, int64_t *stats, mmpde_stream_t stream) {
+    MMPDE_REQUIRE(pos && bins && nbr_out && degree_out && ((uintptr_t)bins & 7) == 0);
+    // the selection is one value per lane: w = max_num_neighbors + 1 <= 64
+    MMPDE_REQUIRE(batches > 0 && batches <= 65535 && n_per > 0 && n_per <= kTiledMax &&
+                  max_num_neighbors > 0 && max_num_neighbors + 1 <= 64 && r > 0.0f);
+    hipLaunchKernelGGL(radius_binned_kernel, dim3((unsigned)ceil_div(n_per, 4), (unsigned)batches),
+                       dim3(256), 0, as_stream(stream), (const float2 *)pos, (const uint32_t *)bins,
+                       bins_layout(n_per), (int)n_per, radius_r2(r), max_num_neighbors + 1, nbr_out, degree_out,
+                       (unsigned long long *)stats);
     MMPDE_RET_LAUNCH();
     return MMPDE_OK;
 }

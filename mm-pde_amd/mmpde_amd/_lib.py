@@ -13,7 +13,7 @@ import os
 import torch
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmmpde_hip.so")
-ABI_VERSION = 12300
+ABI_VERSION = 12301
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_ELU = 0, 1, 2, 3
 PAD_ZEROS, PAD_CIRCULAR = 0, 1
@@ -184,6 +184,7 @@ _SIGS = {
     "mmpde_dmm_mesh_array": (_I, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P]),
     "mmpde_dmm_head_cache_bytes": (_I64, [_I64, _I]),
     "mmpde_radius_graph": (_I, [_P, _I64, _I64, _F, _I, _P, _P, _P]),
+    "mmpde_radius_graph_binned": (_I, [_P, _P, _I64, _I64, _F, _I, _P, _P, _P, _P]),
     "mmpde_dmm_head_prepare": (_I, [_P, _I64, _P, _P, _P, _P]),
     "mmpde_dmm_mesh_graph_cached": (_I, [_P, _P, _I64, _I64, _P, _I, _P, _P, _P, _P, _P, _P]),
     "mmpde_dmm_mesh_array_cached": (_I, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),

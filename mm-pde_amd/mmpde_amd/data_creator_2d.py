@@ -42,6 +42,9 @@ class GraphCreator_FS_2D(nn.Module):  # noqa: N801 - reference name
         # moved-mesh graph and the kNN-30 queries of interpolate / interpolate_pred
         # search; the same tables either way
         self.knn_method = "full"
+        # "scan" or "binned" (ops.radius_graph_nbr): how create_graph's moved-mesh
+        # radius graph searches; the same tables either way
+        self.radius_method = "scan"
 
     # ------------------------------------------------------------------ grids
     def _is_array(self):
@@ -113,6 +116,24 @@ class GraphCreator_FS_2D(nn.Module):  # noqa: N801 - reference name
         if hit is None or hit[0] is not grid:
             hit = (grid, ops.knn_graph_nbr(grid.repeat(batches, 1), batches, self.n))
             self._fixed_graph_cache = {key: hit}
+        return hit[1]
+
+    def fixed_graph(self, grid: torch.Tensor, batches: int):
+        """(nbr, deg) of `batches` copies of the fixed grid for this creator's
+        connect_edge: the kNN-k table of fixed_graph_nbr with deg None, or the
+        radius graph's ragged [n, 33] table and in-degrees (radius(), 32
+        neighbours; cached like fixed_graph_nbr)."""
+        if self.e == "knn":
+            return self.fixed_graph_nbr(grid, batches), None
+        if self.e != "radius":
+            raise ValueError(f"connect_edge {self.e!r}: knn | radius")
+        r = self.radius()
+        key = (grid.data_ptr(), grid._version, tuple(grid.shape), str(grid.device), batches, r)
+        cache = self.__dict__.setdefault("_fixed_radius_cache", {})
+        hit = cache.get(key)
+        if hit is None or hit[0] is not grid:
+            hit = (grid, ops.radius_graph_nbr(grid.repeat(batches, 1), batches, r, 32))
+            self._fixed_radius_cache = {key: hit}
         return hit[1]
 
     # ------------------------------------------------------------------ data
@@ -235,7 +256,8 @@ class GraphCreator_FS_2D(nn.Module):  # noqa: N801 - reference name
         t_nodes = t_b.to(device).repeat_interleave(n)
         deg = None
         if self.e == "radius":   # torch_cluster default max_num_neighbors = 32
-            nbr, deg = ops.radius_graph_nbr(mesh.contiguous(), B, self.radius(), 32)
+            nbr, deg = ops.radius_graph_nbr(mesh.contiguous(), B, self.radius(), 32,
+                                            method=self.radius_method)
         elif mesh_model is None:
             nbr = self.fixed_graph_nbr(grid, B)
         else:

@@ -319,23 +319,57 @@ def knn_graph_moved(pos: torch.Tensor, xi: torch.Tensor, cand, batches: int, k: 
     return (nbr, deg) if count_degenerate else nbr
 
 
-def radius_graph_nbr(pos: torch.Tensor, batches: int, r: float, max_num_neighbors: int = 32):
+RADIUS_METHODS = ("scan", "binned")
+# Trajectories of at least this many points get the rollout's moved-mesh radius
+# graph through cell bins even when the step does not build them anyway
+# (csrc/knn.hip radius_binned_kernel): the smallest measured size from which
+# binning plus the binned search stayed below the index-order scan at every
+# larger size, in both repeats (profiles/radius_times.txt).
+RADIUS_BINNED_MIN_POINTS = 9216
+
+
+def radius_graph_nbr(pos: torch.Tensor, batches: int, r: float, max_num_neighbors: int = 32,
+                     method: str = "scan", bins: torch.Tensor | None = None,
+                     stats: torch.Tensor | None = None):
     """torch_cluster.radius_graph(pos, r, batch, loop=False, max_num_neighbors) for
     `batches` equal contiguous segments (reference data_creator_2d.py:257-258),
     CUDA semantics (first max_num_neighbors + 1 in index order within r, self
     dropped).  Returns (nbr int32 [n, max_num_neighbors + 1] global sources,
-    padded with -1; degree int32 [n])."""
+    padded with -1; degree int32 [n]).  method "binned": the same tables from
+    the cell bins of pos (bins = knn_bins(pos, batches), built here when None;
+    at most 65536 points per trajectory and 63 neighbours); stats: optional
+    int64[2] device counter, += (points examined, queries that took the
+    index-order scan)."""
+    if method not in RADIUS_METHODS:
+        raise ValueError(f"radius method {method!r}; one of {RADIUS_METHODS}")
     L.require_device(pos)
     pos = L.f32c(pos).reshape(-1, 2)
     n = pos.shape[0]
     if n % batches:
         raise ValueError("pos rows must split into equal batch segments")
+    n_per = n // batches
+    if method == "scan":
+        if bins is not None or stats is not None:
+            raise ValueError('bins / stats belong to method="binned"')
+    else:
+        if n_per > KNN_MAX_POINTS:
+            raise ValueError(f"radius_graph binned: {n_per} points per trajectory; at most {KNN_MAX_POINTS}")
+        if not 1 <= max_num_neighbors <= 63:
+            raise ValueError(f"radius_graph binned: max_num_neighbors = {max_num_neighbors}; 1..63")
+        if not r > 0:
+            raise ValueError(f"radius_graph binned: r = {r}; must be positive")
+        bins, stats = _knn_method("binned", bins, stats, pos, batches, n_per)
     w = max_num_neighbors + 1
     nbr = torch.empty((n, w), dtype=torch.int32, device=pos.device)
     deg = torch.empty((n,), dtype=torch.int32, device=pos.device)
-    L.check(L.lib().mmpde_radius_graph(L.ptr(pos), batches, n // batches, float(r),
-                                       max_num_neighbors, L.ptr(nbr), L.ptr(deg),
-                                       L.stream(pos.device)), "mmpde_radius_graph")
+    if method == "binned":
+        L.check(L.lib().mmpde_radius_graph_binned(L.ptr(pos), L.ptr(bins), batches, n_per, float(r),
+                                                  max_num_neighbors, L.ptr(nbr), L.ptr(deg), L.ptr(stats),
+                                                  L.stream(pos.device)), "mmpde_radius_graph_binned")
+    else:
+        L.check(L.lib().mmpde_radius_graph(L.ptr(pos), batches, n_per, float(r),
+                                           max_num_neighbors, L.ptr(nbr), L.ptr(deg),
+                                           L.stream(pos.device)), "mmpde_radius_graph")
     return nbr, deg
 
 

@@ -16,6 +16,10 @@ Burgers (DMM array mode) additionally interpolates u onto the moved mesh first
 moved mesh (data_creator_2d.py:208-209) feeds only graph.y, which no step
 reads, so the rollout (which has no labels) does not compute it.
 
+With connect_edge='radius' (graph_creator.e, data_creator_2d.py:195,226,257-258)
+both graphs are radius graphs instead (radius_graph(mesh, r=gc.radius(), 32
+neighbours): ragged tables nbr_u / deg_u, nbr_m / deg_m).
+
 The fixed-grid GNN runs on a side stream beside the moving-mesh chain.
 
 Rollout: the prediction becomes the next step's input (u <- pred, t index + 1),
@@ -59,7 +63,22 @@ class MMPDERollout:
         self.N = N = self.grid.shape[0]
         self.n = n = batches * N
         self.grid_rep = self.grid.repeat(batches, 1).contiguous()        # [B*N, 2]
-        self.nbr_u = gc.fixed_graph_nbr(self.grid, batches)
+        # connect_edge (reference data_creator_2d.py:257-260): 'knn' graphs of
+        # gc.n neighbours, or 'radius' graphs (gc.radius(), at most 32
+        # neighbours): ragged [n, 33] tables with in-degrees, for the fixed grid
+        # (built once) and the moved mesh (every step)
+        if gc.e not in ("knn", "radius"):
+            raise ValueError(f"connect_edge {gc.e!r}: knn | radius")
+        self.radius_graph = gc.e == "radius"
+        self.radius_r = gc.radius() if self.radius_graph else None
+        self.nbr_u, self.deg_u = gc.fixed_graph(self.grid, batches)
+        self.deg_m = None
+        # the moved-mesh radius graph through the mesh's cell bins
+        # (ops.radius_graph_nbr method="binned"; the same tables): None = whenever
+        # the step bins the mesh anyway (knn_binned) or N >=
+        # ops.RADIUS_BINNED_MIN_POINTS; True / False force it.  Settable before
+        # the first step.
+        self.radius_binned = None
         self.t = gc.time_grid()
         f32 = dict(dtype=torch.float32, device=self.device)
         self.out_u = torch.empty((n, 1), **f32)
@@ -85,9 +104,15 @@ class MMPDERollout:
             # each grid point (exact: csrc/knn.hip knn_cand_kernel, full search
             # where its bound fails).  Burgers' grid is in 'ij' order and xi in
             # 'xy' order, so the query table is built for the grid's own order.
-            self.knn_cand = ops.knn_candidates(self.xi)
-            self.knn_cand_q = (self.knn_cand if self.grid is self.xi
-                               else ops.knn_candidates(self.xi, ref=self.grid))
+            # A radius graph has no kNN-n search: no graph table, skip threshold
+            # or policy role; the query tables are the same either way.
+            if self.radius_graph:
+                self.knn_cand = None
+                self.knn_cand_q = ops.knn_candidates(self.xi, ref=None if self.grid is self.xi else self.grid)
+            else:
+                self.knn_cand = ops.knn_candidates(self.xi)
+                self.knn_cand_q = (self.knn_cand if self.grid is self.xi
+                                   else ops.knn_candidates(self.xi, ref=self.grid))
             # trajectories whose typical displacement exceeds these go straight
             # to the full search (about half the lookups would fail; read once)
             self.knn_skip = ops.knn_skip_threshold(self.xi, self.knn_cand, gc.n + 1, moved_queries=True)
@@ -116,13 +141,14 @@ class MMPDERollout:
             # table vs full search per role, from the share the table answered at
             # an earlier step (ops.KnnTablePolicy: the cost model, no sync)
             self.knn_policy = ops.KnnTablePolicy(
-                self.device, batches, N, ("graph", "query") + (("query1",) if kind == "burgers" else ()))
+                self.device, batches, N, (() if self.radius_graph else ("graph",)) + ("query",)
+                + (("query1",) if kind == "burgers" else ()))
             # Without a candidate table (N > 4096) the per-step searches go
             # through cell bins of the moved mesh instead of scanning the whole
             # trajectory (ops.knn_bins; csrc/knn.hip knn_binned_kernel): the
             # same tables.  Settable before the first step; with it on, the
             # tables above are not consulted.
-            self.knn_binned = self.knn_cand is None and N >= ops.KNN_BINNED_MIN_POINTS
+            self.knn_binned = self.knn_cand_q is None and N >= ops.KNN_BINNED_MIN_POINTS
             self.knn_bins = None     # the moved mesh's bins, rebuilt every step (main1)
             self.knn_bins_1 = None   # burgers mode '1': the fixed grid's bins, built once
             if self.knn_binned:
@@ -160,50 +186,62 @@ class MMPDERollout:
     def _trace(self):
         return self.trace_hook() if self.trace_hook is not None else None
 
-    def _nodes(self, u, xy, nbr, step_idx):
+    def _nodes(self, u, xy, nbr, step_idx, deg=None):
         """The GNN's node inputs with (x, y) positions and one t for every node
         (mmpde_gnn_scales.pos_xy): no (t, x, y) array is filled per step.  Graph
         capture passes the device slot holding t."""
         if isinstance(step_idx, torch.Tensor):
-            return _Nodes(u, xy, nbr, self.N, t_slot=step_idx)
-        return _Nodes(u, xy, nbr, self.N, t=float(self.t[step_idx]))
+            return _Nodes(u, xy, nbr, self.N, t_slot=step_idx, deg=deg)
+        return _Nodes(u, xy, nbr, self.N, t=float(self.t[step_idx]), deg=deg)
 
     # ------------------------------------------------------------ the stages
     # The moving-mesh step is five stages on three streams (every kernel is one
     # of the C-ABI's; each stage runs on the caller's current stream):
     #   side   model(u) on the fixed grid                       needs u
     #   main1  DMM mesh, per-trajectory displacement record     needs u
-    #          (knn_binned: the moved mesh's cell bins instead)
+    #          (knn_binned: the moved mesh's cell bins instead; a binned
+    #          radius graph: the bins as well)
     #   side2  kNN-30 query onto the fixed grid, res_cut(u)     needs main1
-    #   main2  moved-mesh kNN-35 graph (Burgers: u onto the moved mesh), model_b
+    #   main2  moved-mesh kNN-35 or radius graph (Burgers: u onto the moved
+    #          mesh), model_b
     #   final  interpolation + res_cut + model(u) in one kernel  needs all
     def _st_side(self, u_flat, step_idx):
-        nodes_u = self._nodes(u_flat, self.grid_rep, self.nbr_u, step_idx)
+        nodes_u = self._nodes(u_flat, self.grid_rep, self.nbr_u, step_idx, self.deg_u)
         self.model(nodes_u, out=self.out_u, workspace=self.ws_gnn_u, trace=self._trace())
 
     def _ensure_bins(self):
         if self.knn_bins is None:
             nb = L.lib().mmpde_knn_bins_bytes(self.B, self.N)
             self.knn_bins = torch.empty((nb,), dtype=torch.uint8, device=self.device)
-        if self.kind == "burgers" and self.knn_bins_1 is None:
+        if self.kind == "burgers" and self.knn_binned and self.knn_bins_1 is None:
             self.knn_bins_1 = ops.knn_bins(self.grid_rep, self.B)
+
+    def _radius_binned(self) -> bool:
+        if not self.radius_graph:
+            return False
+        if self.radius_binned is None:
+            return bool(self.knn_binned) or self.N >= ops.RADIUS_BINNED_MIN_POINTS
+        return bool(self.radius_binned)
 
     def _st_main1(self, u):
         B = self.B
         self.dmm.mesh(u, self.xi, out=self.mesh, workspace=self.ws_dmm, head_cache=self.dmm_cache)
-        if self.knn_binned:
+        self._rb = self._radius_binned()
+        if self.knn_binned or self._rb:
             # one binning of the moved mesh for the kNN-30 query (side2) and the graph (main2)
             self._ensure_bins()
             ops.knn_bins(self.mesh, B, out=self.knn_bins)
+        if self.knn_binned:
             self._use_g = self._use_q = False
             self._knn_used = {"graph": False, "query": False}
             self._cells = None
             return
         pol = self.knn_policy
-        self._use_g, self._use_q = pol.use_table("graph"), pol.use_table("query")
+        self._use_g = not self.radius_graph and pol.use_table("graph")
+        self._use_q = pol.use_table("query")
         self._knn_used = {"graph": self._use_g, "query": self._use_q}
         self._cells = ops.knn_moved_cells(self.mesh, self.xi, B, out=self.knn_cells) \
-            if self.knn_cand is not None and (self._use_g or self._use_q) else None
+            if self.knn_cand_q is not None and (self._use_g or self._use_q) else None
 
     def _st_side2(self, u):
         B, N = self.B, self.N
@@ -228,7 +266,13 @@ class MMPDERollout:
     def _st_main2(self, u_flat, step_idx):
         B = self.B
         pol, cells, mesh = self.knn_policy, self._cells, self.mesh
-        if self.knn_binned:
+        if self.radius_graph:   # torch_cluster default max_num_neighbors = 32
+            if self._rb:
+                nbr_m, self.deg_m = ops.radius_graph_nbr(mesh, B, self.radius_r, 32, method="binned",
+                                                         bins=self.knn_bins)
+            else:
+                nbr_m, self.deg_m = ops.radius_graph_nbr(mesh, B, self.radius_r, 32)
+        elif self.knn_binned:
             nbr_m = ops.knn_graph_nbr(mesh, B, self.gc.n, method="binned", bins=self.knn_bins)
         elif self._use_g:
             nbr_m = ops.knn_graph_moved(mesh, self.xi, self.knn_cand, B, self.gc.n, self.knn_scratch,
@@ -256,7 +300,7 @@ class MMPDERollout:
             u_m = ops.itp_interp(self.grid_rep, u_flat, mesh, idx1, B, self.itp.packed("1"))
         else:
             u_m = u_flat
-        nodes_m = self._nodes(u_m, mesh, nbr_m, step_idx)
+        nodes_m = self._nodes(u_m, mesh, nbr_m, step_idx, self.deg_m)
         self.model_b(nodes_m, out=self.out_b, workspace=self.ws_gnn, trace=self._trace())
 
     def _st_final(self):
@@ -299,7 +343,7 @@ class MMPDERollout:
 
         if not self.moving_mesh:
             self._g_out = capture("main", cap, lambda: self.model(
-                self._nodes(u_flat, self.grid_rep, self.nbr_u, t), out=self.out_u,
+                self._nodes(u_flat, self.grid_rep, self.nbr_u, t, self.deg_u), out=self.out_u,
                 workspace=self.ws_gnn).reshape(u.shape))
         else:
             capture("side", cap if serial else self.side, lambda: self._st_side(u_flat, t))
@@ -346,7 +390,7 @@ class MMPDERollout:
         u = u.contiguous()
         u_flat = u.reshape(-1)
         if not self.moving_mesh:
-            return self.model(self._nodes(u_flat, self.grid_rep, self.nbr_u, step_idx), out=self.out_u,
+            return self.model(self._nodes(u_flat, self.grid_rep, self.nbr_u, step_idx, self.deg_u), out=self.out_u,
                               workspace=self.ws_gnn, trace=self._trace()).reshape(u.shape)
         cur = torch.cuda.current_stream(self.device)
         side = self.side if self.overlap else cur
@@ -383,7 +427,7 @@ class MMPDERollout:
         moved-mesh kNN lookups the candidate tables answered (the rest went to
         the full search); None for a search the policy ran without the table
         that step (ops.KnnTablePolicy).  Diagnostics: synchronises the device."""
-        if not self.moving_mesh or self.knn_cand is None:
+        if not self.moving_mesh or self.knn_cand_q is None:
             return None
         torch.cuda.synchronize(self.device)
         used = self._knn_used
@@ -395,13 +439,17 @@ class MMPDERollout:
         return tuple(s)
 
     def knn_modes(self):
-        """Per kNN search of the step: 'binned' (knn_binned), else 'table', 'full'
-        or 'probe' (ops.KnnTablePolicy)."""
+        """Per neighbour search of the step: 'binned' (knn_binned), else 'table',
+        'full' or 'probe' (ops.KnnTablePolicy); a radius graph's role is
+        'radius-binned' or 'radius' (radius_binned)."""
         if not self.moving_mesh:
             return {}
+        modes = {"graph": "radius-binned" if self._radius_binned() else "radius"} if self.radius_graph else {}
         if self.knn_binned:
-            return {r: "binned" for r in self.knn_policy.state}
-        return {r: self.knn_policy.mode(r) for r in self.knn_policy.state}
+            modes.update({r: "binned" for r in self.knn_policy.state})
+        else:
+            modes.update({r: self.knn_policy.mode(r) for r in self.knn_policy.state})
+        return modes
 
     def knn_query_ties(self) -> int:
         """Queries of the kNN-30 searches (reference data_creator_2d.py:75-76)
@@ -426,12 +474,13 @@ class _Nodes:
     """The graph fields the solver reads (x, pos, nbr, seg_n = nodes per
     trajectory); pos [n, 2] = (x, y) with t (host float) or t_slot (device
     scalar) for every node, or the reference's [n, 3] (t, x, y)."""
-    __slots__ = ("x", "pos", "nbr", "edge_index", "seg_n", "t", "t_slot")
+    __slots__ = ("x", "pos", "nbr", "deg", "edge_index", "seg_n", "t", "t_slot")
 
-    def __init__(self, x, pos, nbr, seg_n=None, t=None, t_slot=None):
+    def __init__(self, x, pos, nbr, seg_n=None, t=None, t_slot=None, deg=None):
         self.x = x.reshape(-1, 1)
         self.pos = pos
         self.nbr = nbr
+        self.deg = deg   # in-degrees of a ragged table (radius graph), else None
         self.edge_index = None
         self.seg_n = seg_n
         self.t = t
