@@ -783,6 +783,46 @@ int mmpde_dmm_mesh_array_cached(const float *u, const float *xi, int64_t batches
                                 const void *head_cache, void *workspace, float *mesh_out,
                                 mmpde_stream_t stream);
 
+/* The mesh together with the mesh map's Jacobian dx/dxi = I + Hess phi, in eval
+ * mode and in the same pass.  mesh_out is, bit for bit, the mesh of
+ * mmpde_dmm_mesh_*_cached (moving_mesh[_tri], data_creator_2d.py:115-137);
+ * hess_out and det_out replace the four autograd.grad calls and the
+ * determinant of the Monge-Ampere residual, mesh/dmm_utils.py:507-552
+ * (phixx, phixy, phiyy; (1 + phixx)(1 + phiyy) - phixy phiyx).  det <= 0 at a
+ * node: the moved mesh has folded there.
+ *
+ * The Hessian needs one more table of the fixed grid beside Q and J:
+ * K = dJ/dxi [N, L', 3] (components 11, 12, 22), mmpde_dmm_hess_cache_bytes(N,
+ * L') = 3 N L' floats, prepared by mmpde_dmm_hess_prepare (workspace as for
+ * mmpde_dmm_head_prepare; no head cache needed).  Every pointer of
+ * mmpde_dmm_hess_io is nullable: a null cache is computed inside the call
+ * (same bits), a null output is not written.  workspace >=
+ * mmpde_dmm_hess_workspace_bytes(B, N, L, L') (array: max(N, s*s)), which is
+ * the mesh workspace plus room for K and a det scratch.  The reductions are
+ * written (folds_total: added to) by the call itself, in stream order and in
+ * a fixed order: no memset, no synchronisation, capturable, repeatable. */
+typedef struct {
+    const void *head_cache; /* mmpde_dmm_head_prepare's, or null */
+    const void *hess_cache; /* mmpde_dmm_hess_prepare's, or null */
+    float *hess_out;        /* [B*N, 3]: phi_11, phi_12, phi_22 */
+    float *det_out;         /* [B*N] */
+    float *detmin_out;      /* [B]: min over the trajectory's nodes (NaN if any is) */
+    int32_t *folds_out;     /* [B]: nodes with !(det > 0), NaN included */
+    int32_t *folds_total;   /* [B]: folds_out added to it; never reset by the call */
+} mmpde_dmm_hess_io;
+int64_t mmpde_dmm_hess_cache_bytes(int64_t n_per, int hidden);
+int mmpde_dmm_hess_prepare(const float *xi, int64_t n_per, const mmpde_dmm_head *hd,
+                           void *workspace, void *hess_cache, mmpde_stream_t stream);
+int64_t mmpde_dmm_hess_workspace_bytes(int64_t batches, int64_t n_per, int latent, int hidden);
+int mmpde_dmm_mesh_graph_hess(const float *u, const float *grid, int64_t batches, int64_t n_per,
+                              const int32_t *grid_nbr, int k, const mmpde_dmm_graph_branch *br,
+                              const mmpde_dmm_head *hd, const mmpde_dmm_hess_io *io,
+                              void *workspace, float *mesh_out, mmpde_stream_t stream);
+int mmpde_dmm_mesh_array_hess(const float *u, const float *xi, int64_t batches, int64_t n_per,
+                              const mmpde_dmm_array_branch *br, const mmpde_dmm_head *hd,
+                              const mmpde_dmm_hess_io *io, void *workspace, float *mesh_out,
+                              mmpde_stream_t stream);
+
 /* DMM.forward (dmm_model.py:185-219) in two calls, for callers that need phi
  * itself (DMM evaluation, dmm_utils.py) rather than the moved mesh.
  * The branch alone: branch_out [B, L] (L = hd->latent) from u on the fixed

@@ -448,7 +448,7 @@ extern "C" int mmpde_tanh_bwd(const float *dy, const float *t, int64_t n, float 
     return MMPDE_OK;
 }
 
-extern "C" int mmpde_version(void) { return 12301; }
+extern "C" int mmpde_version(void) { return 12302; }
 
 extern "C" int mmpde_traj_mse(const float *pred, const float *labels, int64_t batches, int64_t n_per,
                               float *out, mmpde_stream_t stream) {

@@ -435,6 +435,224 @@ __global__ __launch_bounds__(256) void mesh_vjp_wave_kernel(const float *__restr
     }
 }
 
+// ---------------------------------------------------------------------------
+// The mesh map's Jacobian dx/dxi = I + Hess phi (the left-hand factor of the
+// Monge-Ampere residual, reference mesh/dmm_utils.py:507-552: phixx, phixy,
+// phiyy and (1 + phixx)(1 + phiyy) - phixy phiyx).  With t_k = tanh(P[b,k] +
+// Q[n,k]) and s_m = tanh(T0 xi_n + t0b)_m:
+//     d(phi)/d(xi_d)     = sum_k w_o[k] (1 - t_k^2) J[n,k,d]
+//     Hess phi_{de}(b,n) = sum_k w_o[k] ( -2 t_k (1 - t_k^2) J[n,k,d] J[n,k,e]
+//                                         + (1 - t_k^2) K[n,k,de] )
+//     K[n,k,de] = dJ[n,k,d]/dxi_e = sum_m Gt[m][k] (-2 s_m (1 - s_m^2)) T0[m][d] T0[m][e]
+//     det(b,n)           = (1 + H11)(1 + H22) - H12^2
+// K is symmetric: three components (11, 12, 22), [N, L', 3].  Like Q and J it
+// depends on xi and the weights only (mmpde_dmm_hess_prepare).
+// ---------------------------------------------------------------------------
+// K[n][k][0..2]; one block per grid point (the sibling of jac_kernel).
+__global__ __launch_bounds__(256) void hess_k_kernel(const float *__restrict__ s, int th,
+                                                     const float *__restrict__ gt, int hidden,
+                                                     const float *__restrict__ t0w,
+                                                     float *__restrict__ kout) {
+    __shared__ float c11[64], c12[64], c22[64];
+    const int64_t nidx = blockIdx.x;
+    if (threadIdx.x < th) {
+        const float sv = s[nidx * th + threadIdx.x];
+        const float dd = -2.0f * sv * (1.0f - sv * sv);
+        const float a = t0w[threadIdx.x * 2], b = t0w[threadIdx.x * 2 + 1];
+        c11[threadIdx.x] = dd * a * a;
+        c12[threadIdx.x] = dd * a * b;
+        c22[threadIdx.x] = dd * b * b;
+    }
+    __syncthreads();
+    for (int kk = threadIdx.x; kk < hidden; kk += 256) {
+        float k11 = 0.0f, k12 = 0.0f, k22 = 0.0f;
+        for (int m = 0; m < th; ++m) {
+            const float g = gt[(int64_t)m * hidden + kk];
+            k11 += g * c11[m];
+            k12 += g * c12[m];
+            k22 += g * c22[m];
+        }
+        float *o = kout + (nidx * hidden + kk) * 3;
+        o[0] = k11;
+        o[1] = k12;
+        o[2] = k22;
+    }
+}
+
+// 1 + tr H + (H11 H22 - H12^2): the determinant above with the 1 added last,
+// so that its rounding error is 2^-24 of det itself, not of (1 + |H|)^2
+__device__ __forceinline__ float det_of(float h11, float h12, float h22) {
+    return 1.0f + ((h11 + h22) + __fmaf_rn(h11, h22, -(h12 * h12)));
+}
+
+// One k of the Hessian's three sums, h_de += -2 t g J_d J_e + g K_de with g = w_o
+// (1 - t^2).  Explicit fma's: both kernels below then round alike whatever the
+// compiler contracts around them (a trajectory's rows do not depend on the
+// kernel its batch size selects).
+__device__ __forceinline__ void hess_acc(float t, float g, float2 jj, float k11, float k12, float k22,
+                                         float &h11, float &h12, float &h22) {
+    const float g2 = -2.0f * t * g;
+    const float ax = g2 * jj.x, ay = g2 * jj.y;
+    h11 = __fmaf_rn(g, k11, __fmaf_rn(ax, jj.x, h11));
+    h12 = __fmaf_rn(g, k12, __fmaf_rn(ax, jj.y, h12));
+    h22 = __fmaf_rn(g, k22, __fmaf_rn(ay, jj.y, h22));
+}
+
+// mesh_vjp_kernel with the Hessian's three sums beside the gradient's two: gx and
+// gy are formed and reduced exactly as there (the same mesh bits).  hess / det
+// nullable.
+__global__ __launch_bounds__(256) void mesh_hess_kernel(const float *__restrict__ P,
+                                                        const float *__restrict__ Q,
+                                                        const float2 *__restrict__ jac,
+                                                        const float *__restrict__ kmat,
+                                                        const float *__restrict__ wo,
+                                                        const float2 *__restrict__ xi,
+                                                        int64_t batches, int64_t n_per,
+                                                        int hidden, float2 *__restrict__ mesh,
+                                                        float *__restrict__ hess,
+                                                        float *__restrict__ det) {
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int64_t nidx = blockIdx.x;
+    const float *q = Q + nidx * hidden;
+    const float2 *jr = jac + nidx * hidden;
+    const float *kr = kmat + nidx * hidden * 3;
+    const float2 x = xi[nidx];
+    for (int64_t b = wave; b < batches; b += 4) {
+        const float *pb = P + b * hidden;
+        float gx = 0.0f, gy = 0.0f, h11 = 0.0f, h12 = 0.0f, h22 = 0.0f;
+        for (int kk = lane; kk < hidden; kk += 64) {
+            const float t = tanhf(pb[kk] + q[kk]);
+            const float g = wo[kk] * (1.0f - t * t);
+            const float2 jj = jr[kk];
+            gx += g * jj.x;
+            gy += g * jj.y;
+            hess_acc(t, g, jj, kr[3 * kk], kr[3 * kk + 1], kr[3 * kk + 2], h11, h12, h22);
+        }
+        gx = wave_sum_full(gx);
+        gy = wave_sum_full(gy);
+        h11 = wave_sum_full(h11);
+        h12 = wave_sum_full(h12);
+        h22 = wave_sum_full(h22);
+        if (lane == 0) {
+            const int64_t row = b * n_per + nidx;
+            mesh[row] = make_float2(gx + x.x, gy + x.y);
+            if (hess) {
+                hess[3 * row] = h11;
+                hess[3 * row + 1] = h12;
+                hess[3 * row + 2] = h22;
+            }
+            if (det) det[row] = det_of(h11, h12, h22);
+        }
+    }
+}
+
+// mesh_vjp_wave_kernel with the Hessian: Q[n], J[n], K[n] and w_o once per grid
+// point into registers (7 KPL values per lane), P in LDS, one tanh per (b, n, k);
+// gx and gy as there (the same mesh bits).
+template <int KPL>
+__global__ __launch_bounds__(256) void mesh_hess_wave_kernel(const float *__restrict__ P,
+                                                             const float *__restrict__ Q,
+                                                             const float2 *__restrict__ jac,
+                                                             const float *__restrict__ kmat,
+                                                             const float *__restrict__ wo,
+                                                             const float2 *__restrict__ xi,
+                                                             int batches, int n_per,
+                                                             float2 *__restrict__ mesh,
+                                                             float *__restrict__ hess,
+                                                             float *__restrict__ det) {
+    extern __shared__ float sP[];  // [batches][64 KPL]
+    constexpr int HID = 64 * KPL;
+    for (int i = threadIdx.x; i < batches * HID; i += 256) sP[i] = P[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int nidx = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (nidx >= n_per) return;  // wave-uniform, after the only barrier
+    float q[KPL], w[KPL], k11[KPL], k12[KPL], k22[KPL];
+    float2 jj[KPL];
+#pragma unroll
+    for (int i = 0; i < KPL; ++i) {
+        const int kk = lane + 64 * i;
+        q[i] = Q[(int64_t)nidx * HID + kk];
+        jj[i] = jac[(int64_t)nidx * HID + kk];
+        const float *kr = kmat + ((int64_t)nidx * HID + kk) * 3;
+        k11[i] = kr[0];
+        k12[i] = kr[1];
+        k22[i] = kr[2];
+        w[i] = wo[kk];
+    }
+    const float2 x = xi[nidx];
+    for (int b = 0; b < batches; ++b) {
+        const float *pb = sP + b * HID;
+        float gx = 0.0f, gy = 0.0f, h11 = 0.0f, h12 = 0.0f, h22 = 0.0f;
+#pragma unroll
+        for (int i = 0; i < KPL; ++i) {
+            const float t = tanhf(pb[lane + 64 * i] + q[i]);
+            const float g = w[i] * (1.0f - t * t);
+            gx += g * jj[i].x;
+            gy += g * jj[i].y;
+            hess_acc(t, g, jj[i], k11[i], k12[i], k22[i], h11, h12, h22);
+        }
+        gx = wave_sum_full(gx);
+        gy = wave_sum_full(gy);
+        h11 = wave_sum_full(h11);
+        h12 = wave_sum_full(h12);
+        h22 = wave_sum_full(h22);
+        if (lane == 0) {
+            const int64_t row = (int64_t)b * n_per + nidx;
+            mesh[row] = make_float2(gx + x.x, gy + x.y);
+            if (hess) {
+                hess[3 * row] = h11;
+                hess[3 * row + 1] = h12;
+                hess[3 * row + 2] = h22;
+            }
+            if (det) det[row] = det_of(h11, h12, h22);
+        }
+    }
+}
+
+// detmin[b] = min_n det (NaN if any det is NaN), folds[b] = #{n : !(det > 0)} (a
+// NaN det counts as folded), folds_total[b] += folds[b]; one block per
+// trajectory, a fixed reduction order (every output written, none read but
+// folds_total: no initialisation, the same bits on every run).  All nullable.
+__global__ __launch_bounds__(256) void det_reduce_kernel(const float *__restrict__ det,
+                                                         int64_t n_per,
+                                                         float *__restrict__ detmin,
+                                                         int32_t *__restrict__ folds,
+                                                         int32_t *__restrict__ folds_total) {
+    __shared__ float smin[4];
+    __shared__ int scnt[4], snan[4];
+    const float *d = det + (int64_t)blockIdx.x * n_per;
+    float mn = INFINITY;
+    int cnt = 0, nan = 0;
+    for (int64_t i = threadIdx.x; i < n_per; i += 256) {
+        const float v = d[i];
+        cnt += !(v > 0.0f);
+        nan |= v != v;
+        mn = fminf(mn, v);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        mn = fminf(mn, __shfl_xor(mn, o, 64));
+        cnt += __shfl_xor(cnt, o, 64);
+        nan |= __shfl_xor(nan, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        smin[threadIdx.x >> 6] = mn;
+        scnt[threadIdx.x >> 6] = cnt;
+        snan[threadIdx.x >> 6] = nan;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        mn = fminf(fminf(smin[0], smin[1]), fminf(smin[2], smin[3]));
+        cnt = scnt[0] + scnt[1] + scnt[2] + scnt[3];
+        nan = snan[0] | snan[1] | snan[2] | snan[3];
+        if (detmin) detmin[blockIdx.x] = nan ? __builtin_nanf("") : mn;
+        if (folds) folds[blockIdx.x] = cnt;
+        if (folds_total) folds_total[blockIdx.x] += cnt;
+    }
+}
+
 // phi[i] = w_o . tanh(P[b] + Q[i]) + b_o2, b = i / per (out_nn = DenseNet[2L, L', 1]
 // on cat(branch_b, trunk(grid_i)), dmm_model.py:190,213); second[i] = the tanh
 // row (rf=True's second_out).  One wave per grid row.
@@ -549,6 +767,62 @@ int dmm_head(const float *branch, const float *xi, int64_t batches, int64_t n_pe
                            hd->o1_w, (const float2 *)xi, batches, n_per, Lp, (float2 *)mesh_out);
     }
     MMPDE_RET_LAUNCH();
+    return MMPDE_OK;
+}
+
+// Hessian cache layout: K [N, L', 3].
+int64_t hess_cache_floats(int64_t n_per, int hidden) { return 3 * n_per * hidden; }
+// what the _hess entries take past the mesh workspace: K, then a det scratch
+int64_t hess_extra_floats(int64_t batches, int64_t n_per, int hidden) {
+    return hess_cache_floats(n_per, hidden) + ((batches * n_per + 3) & ~int64_t(3)) + 64;
+}
+
+// dmm_head with the Hessian: branch [B, L] -> mesh [B*N, 2], hess, det and the
+// per-trajectory reductions.  extra: hess_extra_floats past the mesh workspace.
+// Either cache may be null: the grid side is then computed here (s and Gt, which
+// K is made from, live only in the workspace, so a missing K recomputes them
+// beside a cached Q, J; the kernels and so the bits are those of the caches).
+int dmm_head_hess(const float *branch, const float *xi, int64_t batches, int64_t n_per,
+                  const mmpde_dmm_head *hd, float *ws, float *extra, const mmpde_dmm_hess_io *io,
+                  float *mesh_out, hipStream_t st, float *sk, int64_t skf) {
+    const int L = hd->latent, Lp = hd->hidden, th = hd->th;
+    if (!head_ok(hd)) return MMPDE_ERR_UNSUPPORTED;
+    HeadWs w = carve_head(ws, batches, n_per, L, Lp, th);
+    const float *hc = (const float *)io->head_cache;
+    const float *q = hc ? hc : w.q;
+    const float2 *jac = hc ? (const float2 *)(hc + n_per * Lp) : w.jac;
+    const float *kmat = io->hess_cache ? (const float *)io->hess_cache : extra;
+    float *det = io->det_out ? io->det_out : extra + hess_cache_floats(n_per, Lp);
+    int rc;
+    if (!hc || !io->hess_cache) {
+        rc = dmm_head_grid(xi, n_per, hd, w, w.q, w.jac, st);
+        if (rc) return rc;
+    }
+    if (!io->hess_cache) {
+        hipLaunchKernelGGL(hess_k_kernel, dim3((unsigned)n_per), dim3(256), 0, st, w.s, th, w.gt, Lp,
+                           hd->t0_w, extra);
+        MMPDE_RET_LAUNCH();
+    }
+    // P = Wb . branch + b_o1 (Wb = out_nn.layers.0.weight[:, :L], row stride 2L)
+    rc = mmpde_linear_skinny_ws(branch, L, batches, L, hd->o0_w, 2 * L, hd->o0_b, Lp, MMPDE_ACT_NONE, w.p,
+                                Lp, sk, skf * (int64_t)sizeof(float), st);
+    if (rc) return rc;
+    const size_t lds = (size_t)batches * Lp * sizeof(float);
+    if (Lp == 512 && lds <= 65536) {
+        hipLaunchKernelGGL(mesh_hess_wave_kernel<8>, dim3((unsigned)ceil_div(n_per, 4)), dim3(256),
+                           lds, st, w.p, q, jac, kmat, hd->o1_w, (const float2 *)xi, (int)batches,
+                           (int)n_per, (float2 *)mesh_out, io->hess_out, det);
+    } else {
+        hipLaunchKernelGGL(mesh_hess_kernel, dim3((unsigned)n_per), dim3(256), 0, st, w.p, q, jac, kmat,
+                           hd->o1_w, (const float2 *)xi, batches, n_per, Lp, (float2 *)mesh_out,
+                           io->hess_out, det);
+    }
+    MMPDE_RET_LAUNCH();
+    if (io->detmin_out || io->folds_out || io->folds_total) {
+        hipLaunchKernelGGL(det_reduce_kernel, dim3((unsigned)batches), dim3(256), 0, st, det, n_per,
+                           io->detmin_out, io->folds_out, io->folds_total);
+        MMPDE_RET_LAUNCH();
+    }
     return MMPDE_OK;
 }
 
@@ -712,15 +986,16 @@ int array_branch(const float *u, int64_t batches, const mmpde_dmm_array_branch *
 int64_t array_n_eff(int64_t n_per, int s) { return n_per > (int64_t)s * s ? n_per : (int64_t)s * s; }
 }  // namespace
 
-extern "C" int mmpde_dmm_mesh_graph_cached(const float *u, const float *grid, int64_t batches,
-                                           int64_t n_per, const int32_t *grid_nbr, int k,
-                                           const mmpde_dmm_graph_branch *br,
-                                           const mmpde_dmm_head *hd, const void *head_cache,
-                                           void *workspace, float *mesh_out,
-                                           mmpde_stream_t stream) {
+namespace {
+// the graph-mode mesh call; io: the Hessian outputs and caches (_hess), or null
+int mesh_graph(const float *u, const float *grid, int64_t batches, int64_t n_per,
+               const int32_t *grid_nbr, int k, const mmpde_dmm_graph_branch *br,
+               const mmpde_dmm_head *hd, const void *head_cache, const mmpde_dmm_hess_io *io,
+               void *workspace, float *mesh_out, mmpde_stream_t stream) {
     MMPDE_REQUIRE(u && grid && grid_nbr && br && hd && workspace && mesh_out);
     MMPDE_REQUIRE(batches > 0 && n_per > k && k > 0 && br->n_gnn_layers >= 0 &&
                   br->n_gnn_layers <= 3 && al16(workspace));
+    if (io && !head_ok(hd)) return MMPDE_ERR_UNSUPPORTED;  // before any launch
     hipStream_t st = as_stream(stream);
     float *ws = (float *)workspace;
     float *sk = ws + dmm_base_floats(batches, n_per, hd->latent, hd->hidden);
@@ -732,8 +1007,20 @@ extern "C" int mmpde_dmm_mesh_graph_cached(const float *u, const float *grid, in
     float *head_ws = branch + ((batches * hd->latent + 3) & ~int64_t(3));
     int rc = graph_branch(u, grid, batches, n_per, grid_nbr, k, br, hd->latent, ws, sk, skf, branch, &end, st);
     if (rc) return rc;
+    if (io) return dmm_head_hess(branch, grid, batches, n_per, hd, head_ws, sk + skf, io, mesh_out, st, sk, skf);
     return dmm_head(branch, grid, batches, n_per, hd, head_ws, (const float *)head_cache, mesh_out,
                     st, sk, skf);
+}
+}  // namespace
+
+extern "C" int mmpde_dmm_mesh_graph_cached(const float *u, const float *grid, int64_t batches,
+                                           int64_t n_per, const int32_t *grid_nbr, int k,
+                                           const mmpde_dmm_graph_branch *br,
+                                           const mmpde_dmm_head *hd, const void *head_cache,
+                                           void *workspace, float *mesh_out,
+                                           mmpde_stream_t stream) {
+    return mesh_graph(u, grid, batches, n_per, grid_nbr, k, br, hd, head_cache, nullptr, workspace,
+                      mesh_out, stream);
 }
 
 extern "C" int mmpde_dmm_mesh_array(const float *u, const float *xi, int64_t batches,
@@ -744,13 +1031,14 @@ extern "C" int mmpde_dmm_mesh_array(const float *u, const float *xi, int64_t bat
                                        stream);
 }
 
-extern "C" int mmpde_dmm_mesh_array_cached(const float *u, const float *xi, int64_t batches,
-                                           int64_t n_per, const mmpde_dmm_array_branch *br,
-                                           const mmpde_dmm_head *hd, const void *head_cache,
-                                           void *workspace, float *mesh_out,
-                                           mmpde_stream_t stream) {
+namespace {
+// the array-mode mesh call; io: the Hessian outputs and caches (_hess), or null
+int mesh_array(const float *u, const float *xi, int64_t batches, int64_t n_per,
+               const mmpde_dmm_array_branch *br, const mmpde_dmm_head *hd, const void *head_cache,
+               const mmpde_dmm_hess_io *io, void *workspace, float *mesh_out, mmpde_stream_t stream) {
     MMPDE_REQUIRE(u && xi && br && hd && workspace && mesh_out && batches > 0 && n_per > 0);
     MMPDE_REQUIRE(br->s >= 5 && al16(workspace));
+    if (io && !head_ok(hd)) return MMPDE_ERR_UNSUPPORTED;  // before any launch
     hipStream_t st = as_stream(stream);
     float *ws = (float *)workspace;
     float *sk = ws + dmm_base_floats(batches, array_n_eff(n_per, br->s), hd->latent, hd->hidden);
@@ -764,7 +1052,62 @@ extern "C" int mmpde_dmm_mesh_array_cached(const float *u, const float *xi, int6
     float *head_ws = branch + up4(batches * hd->latent);
     int rc = array_branch(u, batches, br, hd->latent, ws, sk, skf, branch, &end, st);
     if (rc) return rc;
+    if (io) return dmm_head_hess(branch, xi, batches, n_per, hd, head_ws, sk + skf, io, mesh_out, st, sk, skf);
     return dmm_head(branch, xi, batches, n_per, hd, head_ws, (const float *)head_cache, mesh_out, st, sk, skf);
+}
+}  // namespace
+
+extern "C" int mmpde_dmm_mesh_array_cached(const float *u, const float *xi, int64_t batches,
+                                           int64_t n_per, const mmpde_dmm_array_branch *br,
+                                           const mmpde_dmm_head *hd, const void *head_cache,
+                                           void *workspace, float *mesh_out,
+                                           mmpde_stream_t stream) {
+    return mesh_array(u, xi, batches, n_per, br, hd, head_cache, nullptr, workspace, mesh_out, stream);
+}
+
+// ---------------------------------------------------------------------------
+// The mesh with its Jacobian (Hess phi, det, the fold counts)
+// ---------------------------------------------------------------------------
+extern "C" int64_t mmpde_dmm_hess_cache_bytes(int64_t n_per, int hidden) {
+    return n_per > 0 && hidden > 0 ? hess_cache_floats(n_per, hidden) * (int64_t)sizeof(float) : 0;
+}
+
+extern "C" int64_t mmpde_dmm_hess_workspace_bytes(int64_t batches, int64_t n_per, int latent,
+                                                  int hidden) {
+    return mmpde_dmm_workspace_bytes(batches, n_per, latent, hidden) +
+           hess_extra_floats(batches, n_per, hidden) * (int64_t)sizeof(float);
+}
+
+extern "C" int mmpde_dmm_hess_prepare(const float *xi, int64_t n_per, const mmpde_dmm_head *hd,
+                                      void *workspace, void *hess_cache, mmpde_stream_t stream) {
+    MMPDE_REQUIRE(xi && hd && workspace && hess_cache && n_per > 0 && al16(workspace));
+    if (!head_ok(hd)) return MMPDE_ERR_UNSUPPORTED;
+    hipStream_t st = as_stream(stream);
+    HeadWs w = carve_head((float *)workspace, 1, n_per, hd->latent, hd->hidden, hd->th);
+    const int rc = dmm_head_grid(xi, n_per, hd, w, w.q, w.jac, st);  // s and Gt
+    if (rc) return rc;
+    hipLaunchKernelGGL(hess_k_kernel, dim3((unsigned)n_per), dim3(256), 0, st, w.s, hd->th, w.gt,
+                       hd->hidden, hd->t0_w, (float *)hess_cache);
+    MMPDE_RET_LAUNCH();
+    return MMPDE_OK;
+}
+
+extern "C" int mmpde_dmm_mesh_graph_hess(const float *u, const float *grid, int64_t batches,
+                                         int64_t n_per, const int32_t *grid_nbr, int k,
+                                         const mmpde_dmm_graph_branch *br,
+                                         const mmpde_dmm_head *hd, const mmpde_dmm_hess_io *io,
+                                         void *workspace, float *mesh_out, mmpde_stream_t stream) {
+    MMPDE_REQUIRE(io);
+    return mesh_graph(u, grid, batches, n_per, grid_nbr, k, br, hd, nullptr, io, workspace, mesh_out,
+                      stream);
+}
+
+extern "C" int mmpde_dmm_mesh_array_hess(const float *u, const float *xi, int64_t batches,
+                                         int64_t n_per, const mmpde_dmm_array_branch *br,
+                                         const mmpde_dmm_head *hd, const mmpde_dmm_hess_io *io,
+                                         void *workspace, float *mesh_out, mmpde_stream_t stream) {
+    MMPDE_REQUIRE(io);
+    return mesh_array(u, xi, batches, n_per, br, hd, nullptr, io, workspace, mesh_out, stream);
 }
 
 // ---------------------------------------------------------------------------

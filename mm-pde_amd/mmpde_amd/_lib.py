@@ -13,7 +13,7 @@ import os
 import torch
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmmpde_hip.so")
-ABI_VERSION = 12301
+ABI_VERSION = 12302
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_ELU = 0, 1, 2, 3
 PAD_ZEROS, PAD_CIRCULAR = 0, 1
@@ -84,6 +84,12 @@ class DmmArrayBranch(ctypes.Structure):
 class DmmHead(ctypes.Structure):
     _fields_ = [("t0_w", _P), ("t0_b", _P), ("t1_w", _P), ("t1_b", _P), ("th", _I),
                 ("latent", _I), ("o0_w", _P), ("o0_b", _P), ("o1_w", _P), ("hidden", _I)]
+
+
+class DmmHessIO(ctypes.Structure):
+    """mmpde_dmm_hess_io: the caches and outputs of mmpde_dmm_mesh_*_hess, all nullable."""
+    _fields_ = [(n, _P) for n in ("head_cache", "hess_cache", "hess_out", "det_out", "detmin_out",
+                                  "folds_out", "folds_total")]
 
 
 class ItpMlp(ctypes.Structure):
@@ -188,6 +194,11 @@ _SIGS = {
     "mmpde_dmm_head_prepare": (_I, [_P, _I64, _P, _P, _P, _P]),
     "mmpde_dmm_mesh_graph_cached": (_I, [_P, _P, _I64, _I64, _P, _I, _P, _P, _P, _P, _P, _P]),
     "mmpde_dmm_mesh_array_cached": (_I, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+    "mmpde_dmm_hess_cache_bytes": (_I64, [_I64, _I]),
+    "mmpde_dmm_hess_prepare": (_I, [_P, _I64, _P, _P, _P, _P]),
+    "mmpde_dmm_hess_workspace_bytes": (_I64, [_I64, _I64, _I, _I]),
+    "mmpde_dmm_mesh_graph_hess": (_I, [_P, _P, _I64, _I64, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "mmpde_dmm_mesh_array_hess": (_I, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),
     "mmpde_dmm_branch_graph": (_I, [_P, _P, _I64, _I64, _P, _I, _P, _P, _P, _P, _P]),
     "mmpde_dmm_branch_array": (_I, [_P, _I64, _P, _P, _P, _P, _P]),
     "mmpde_dmm_phi_workspace_bytes": (_I64, [_I64, _I64, _I, _I, _I]),

@@ -11,6 +11,10 @@ x = xi + d(phi)/d(xi) that GraphCreator_FS_2D.moving_mesh[_tri] obtains with
 two autograd.grad calls (data_creator_2d.py:106-107,130-131).  ``DMM.mesh``
 returns exactly that through an analytic vector-Jacobian product
 (mmpde_dmm_mesh_graph / mmpde_dmm_mesh_array; derivation in dmm.hip).
+``DMM.mesh_hess`` returns the same mesh together with the mesh map's Jacobian
+dx/dxi = I + Hess phi, its determinant and per-trajectory fold counts
+(mmpde_dmm_mesh_*_hess: the reference's phixx, phixy, phiyy of
+mesh/dmm_utils.py:507-552, in eval mode and without autograd).
 ``DMM.forward`` (phi, and rf=True's second output) runs the branch and the
 head on the same kernels (mmpde_dmm_branch_*, mmpde_dmm_phi); ``DenseNet`` /
 ``ConvNet`` forwards run on the skinny-linear and conv kernels.
@@ -420,3 +424,96 @@ class DMM(nn.Module):
                 L.ptr(u), L.ptr(xi), B, N, ctypes.byref(bp), ctypes.byref(hd), hc,
                 L.ptr(workspace), L.ptr(out), st), "mmpde_dmm_mesh_array")
         return out
+
+    # ----------------------------------------------------------------- the mesh Jacobian
+    def hess_cache(self, xi: torch.Tensor, workspace: torch.Tensor | None = None) -> torch.Tensor:
+        """K = dJ/dxi [N, L', 3], the table of xi and the weights that the Hessian
+        needs beside head_cache's Q and J: prepared once for a rollout over a
+        fixed grid and passed to mesh_hess(..., hess_cache=).  Recompute it after
+        changing weights."""
+        L.require_device(xi)
+        _, hd = self.device_params()
+        xi = L.f32c(xi).reshape(-1, 2)
+        N = xi.shape[0]
+        nb = L.lib().mmpde_dmm_workspace_bytes(1, N, hd.latent, hd.hidden)
+        if workspace is None:
+            workspace = torch.empty((nb // 4,), dtype=torch.float32, device=xi.device)
+        else:
+            L.require_device(workspace)
+            if workspace.numel() * workspace.element_size() < nb:
+                raise ValueError("workspace is smaller than mmpde_dmm_workspace_bytes")
+        cache = torch.empty((L.lib().mmpde_dmm_hess_cache_bytes(N, hd.hidden) // 4,),
+                            dtype=torch.float32, device=xi.device)
+        L.check(L.lib().mmpde_dmm_hess_prepare(L.ptr(xi), N, ctypes.byref(hd), L.ptr(workspace),
+                                               L.ptr(cache), L.stream(xi.device)),
+                "mmpde_dmm_hess_prepare")
+        return cache
+
+    def mesh_hess(self, u: torch.Tensor, xi: torch.Tensor, out: torch.Tensor | None = None,
+                  hess_out: torch.Tensor | None = None, det_out: torch.Tensor | None = None,
+                  workspace: torch.Tensor | None = None,
+                  head_cache: torch.Tensor | None = None,
+                  hess_cache: torch.Tensor | None = None,
+                  nbr: torch.Tensor | None = None, folds_total: torch.Tensor | None = None,
+                  detmin_out: torch.Tensor | None = None, folds_out: torch.Tensor | None = None):
+        """mesh(u, xi) together with the mesh map's Jacobian dx/dxi = I + Hess phi
+        (reference mesh/dmm_utils.py:507-552's phixx, phixy, phiyy and determinant,
+        without autograd and in eval mode).  Arguments as for mesh; hess_cache:
+        hess_cache(xi) of the same xi and weights, or None; folds_total: a [B]
+        int32 counter the call adds this call's folds to (never reset here).
+        Returns (mesh [B*N, 2], hess [B*N, 3] = (phi_11, phi_12, phi_22),
+        det [B*N], detmin [B], folds [B] int32): det <= 0 (or NaN) at a node means
+        the moved mesh has folded there; folds counts those nodes per trajectory.
+        The mesh is bit for bit that of mesh()."""
+        L.require_device(u, xi)
+        bp, hd = self.device_params()
+        u = L.f32c(u)
+        xi = L.f32c(xi).reshape(-1, 2)
+        B, N = u.shape[0], xi.shape[0]
+        lib = L.lib()
+        ne = N if self.mode == "graph" else max(N, self.branch.s ** 2)  # array: xi may be coarser
+        nb = lib.mmpde_dmm_hess_workspace_bytes(B, ne, hd.latent, hd.hidden)
+        if workspace is None:
+            workspace = torch.empty((nb // 4,), dtype=torch.float32, device=u.device)
+        else:
+            L.require_device(workspace)
+            if workspace.numel() * workspace.element_size() < nb:
+                raise ValueError("workspace is smaller than mmpde_dmm_hess_workspace_bytes")
+        for name, cache, need in (("head_cache", head_cache, lib.mmpde_dmm_head_cache_bytes(N, hd.hidden)),
+                                  ("hess_cache", hess_cache, lib.mmpde_dmm_hess_cache_bytes(N, hd.hidden))):
+            if cache is not None:
+                L.require_device(cache)
+                if cache.dtype != torch.float32 or not cache.is_contiguous() or cache.numel() * 4 < need:
+                    raise ValueError(f"{name} is smaller than mmpde_dmm_{name}_bytes")
+
+        def buf(t, shape, dtype, what):
+            if t is None:
+                return torch.empty(shape, dtype=dtype, device=u.device)
+            L.require_device(t)
+            if t.dtype != dtype or not t.is_contiguous() or t.numel() != torch.Size(shape).numel():
+                raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)}")
+            return t
+
+        out = buf(out, (B * N, 2), torch.float32, "out")
+        hess_out = buf(hess_out, (B * N, 3), torch.float32, "hess_out")
+        det_out = buf(det_out, (B * N,), torch.float32, "det_out")
+        detmin = buf(detmin_out, (B,), torch.float32, "detmin_out")
+        folds = buf(folds_out, (B,), torch.int32, "folds_out")
+        if folds_total is not None:
+            folds_total = buf(folds_total, (B,), torch.int32, "folds_total")
+        io = L.DmmHessIO(L.ptr(head_cache), L.ptr(hess_cache), L.ptr(hess_out), L.ptr(det_out),
+                         L.ptr(detmin), L.ptr(folds), L.ptr(folds_total))
+        st = L.stream(u.device)
+        if self.mode == "graph":
+            nbr = self.grid_nbr(xi) if nbr is None else self._local_nbr(nbr, N, u.device)
+            L.check(lib.mmpde_dmm_mesh_graph_hess(
+                L.ptr(u), L.ptr(xi), B, N, L.ptr(nbr), nbr.shape[1], ctypes.byref(bp),
+                ctypes.byref(hd), ctypes.byref(io), L.ptr(workspace), L.ptr(out), st),
+                "mmpde_dmm_mesh_graph_hess")
+        else:
+            if nbr is not None:
+                raise ValueError("nbr is a graph-mode argument")
+            L.check(lib.mmpde_dmm_mesh_array_hess(
+                L.ptr(u), L.ptr(xi), B, N, ctypes.byref(bp), ctypes.byref(hd), ctypes.byref(io),
+                L.ptr(workspace), L.ptr(out), st), "mmpde_dmm_mesh_array_hess")
+        return out, hess_out, det_out, detmin, folds

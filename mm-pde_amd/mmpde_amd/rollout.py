@@ -28,6 +28,11 @@ SURVEY.md §3); ``step`` is that one-step forward.  What depends only on the
 fixed grid and the weights is built once at construction: the fixed-grid graph
 (``nbr_u``) and the DMM head's grid side (trunk(xi), Q, J; ``dmm_cache``).
 Changing weights after construction needs a new engine.
+
+A DMM fed its own predictions can fold the mesh (det(dx/dxi) <= 0 at a node),
+after which the moved-mesh graph and the interpolation are built on tangled
+points.  ``mesh_check = True`` makes the DMM stage report that
+(``mesh_report()``); it corrects nothing.
 """
 from __future__ import annotations
 
@@ -58,6 +63,11 @@ class MMPDERollout:
         # stream priorities (set_priorities): the moving-mesh chain and the
         # kNN-30 query at high priority, the fixed-grid model at low priority
         self.priorities = PRIORITIES
+        # the fold monitor: the DMM step also computes det(dx/dxi) = det(I + Hess phi)
+        # at every node and counts the nodes where it is not positive (the moved
+        # mesh has folded there; mesh_report()).  The mesh, and so the step, keep
+        # their bits.  Settable before the first step and before enable_graph.
+        self.mesh_check = False
         gc = graph_creator
         self.grid = gc.uniform_grid(self.device).contiguous()           # [N, 2]
         self.N = N = self.grid.shape[0]
@@ -99,6 +109,11 @@ class MMPDERollout:
                 itp.packed(mode)
             # the DMM head's grid side depends on xi and the weights only
             self.dmm_cache = dmm.head_cache(self.xi, workspace=self.ws_dmm)
+            # the fold monitor (mesh_check): its table K = dJ/dxi and its buffers
+            # are built on the first checked step, a default engine holds none
+            self.hess_cache = None
+            self.mesh_hess = self.mesh_det = self.mesh_detmin = None
+            self.mesh_folds = self.mesh_folds_total = None
             # the moved-mesh graph from the 128 nearest of each xi point, the
             # kNN-30 query of the fixed grid from the 128 nearest xi points of
             # each grid point (exact: csrc/knn.hip knn_cand_kernel, full search
@@ -223,9 +238,34 @@ class MMPDERollout:
             return bool(self.knn_binned) or self.N >= ops.RADIUS_BINNED_MIN_POINTS
         return bool(self.radius_binned)
 
+    def _ensure_mesh_check(self):
+        """The monitor's table and buffers (once): K = dJ/dxi of the fixed grid,
+        a workspace with room for the det scratch, Hess phi, det and the counts."""
+        if self.hess_cache is not None:
+            return
+        hd = self.dmm.device_params()[1]
+        f32 = dict(dtype=torch.float32, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        self.hess_cache = self.dmm.hess_cache(self.xi, workspace=self.ws_dmm)
+        nb = L.lib().mmpde_dmm_hess_workspace_bytes(self.B, self.N, hd.latent, hd.hidden)
+        self.ws_dmm_hess = torch.empty((nb // 4,), **f32)
+        self.mesh_hess = torch.empty((self.n, 3), **f32)
+        self.mesh_det = torch.empty((self.n,), **f32)
+        self.mesh_detmin = torch.empty((self.B,), **f32)
+        self.mesh_folds = torch.zeros((self.B,), **i32)
+        self.mesh_folds_total = torch.zeros((self.B,), **i32)
+
     def _st_main1(self, u):
         B = self.B
-        self.dmm.mesh(u, self.xi, out=self.mesh, workspace=self.ws_dmm, head_cache=self.dmm_cache)
+        if self.mesh_check:
+            # the same mesh bits, with Hess phi, det and the fold counts beside them
+            self._ensure_mesh_check()
+            self.dmm.mesh_hess(u, self.xi, out=self.mesh, hess_out=self.mesh_hess, det_out=self.mesh_det,
+                               workspace=self.ws_dmm_hess, head_cache=self.dmm_cache,
+                               hess_cache=self.hess_cache, folds_total=self.mesh_folds_total,
+                               detmin_out=self.mesh_detmin, folds_out=self.mesh_folds)
+        else:
+            self.dmm.mesh(u, self.xi, out=self.mesh, workspace=self.ws_dmm, head_cache=self.dmm_cache)
         self._rb = self._radius_binned()
         if self.knn_binned or self._rb:
             # one binning of the moved mesh for the kNN-30 query (side2) and the graph (main2)
@@ -324,6 +364,8 @@ class MMPDERollout:
         measurement baseline of the side streams' overlap)."""
         if self.trace_hook is not None:
             raise ValueError("graph replay records no per-kernel events; clear trace_hook")
+        if self.moving_mesh and self.mesh_check:
+            self._ensure_mesh_check()   # allocations and the K table stay out of the capture
         self._g_u = torch.empty_like(u_like).contiguous()
         self._g_u.copy_(u_like)
         self._g_t = torch.zeros((1,), dtype=torch.float32, device=self.device)
@@ -461,6 +503,19 @@ class MMPDERollout:
             return 0
         torch.cuda.synchronize(self.device)
         return int(self.knn_ties.item())
+
+    def mesh_report(self):
+        """The fold monitor's record (mesh_check = True): per trajectory, the
+        last step's number of folded nodes (det(dx/dxi) <= 0 or NaN: the moved
+        mesh is not a mesh there) and its smallest det, and the folded nodes
+        summed over every checked step since construction.  The monitor only
+        reports; the step does not change.  None before the first checked step.
+        Synchronises."""
+        if not self.moving_mesh or self.hess_cache is None:
+            return None
+        torch.cuda.synchronize(self.device)
+        return {"folds": self.mesh_folds.tolist(), "detmin": self.mesh_detmin.tolist(),
+                "folds_total": self.mesh_folds_total.tolist()}
 
     def rollout(self, u0: torch.Tensor, start_step: int, n_steps: int):
         """Feed each prediction back as the next input; returns the final state."""
