@@ -823,6 +823,50 @@ int mmpde_dmm_mesh_array_hess(const float *u, const float *xi, int64_t batches, 
                               const mmpde_dmm_hess_io *io, void *workspace, float *mesh_out,
                               mmpde_stream_t stream);
 
+/* The fold guard: the relaxation that ends moving_mesh[_tri],
+ * x = alpha * x + (1 - alpha) * xi (data_creator_2d.py:109-111,133-135, where
+ * alpha = 1 is hard-coded), with alpha a parameter and, with floor > 0, chosen
+ * per trajectory so that the moved mesh does not fold.  The relaxed map's
+ * Jacobian is I + alpha Hess phi; with lam_b = min over the trajectory's nodes
+ * of the smaller eigenvalue of Hess phi,
+ *     lambda_n = (h11 + h22) / 2 - sqrt(((h11 - h22) / 2)^2 + h12^2),
+ * the step is alpha_b = alpha_max where 1 + alpha_max lam_b >= floor and
+ * (1 - floor) / (-lam_b) otherwise: the largest step that keeps the smallest
+ * eigenvalue of dx/dxi at or above floor at every node.  A trajectory whose
+ * Hessian holds a NaN gets alpha_b = 0 (it stays on the fixed grid).
+ * floor <= 0: the guard is off, alpha_b = alpha_max and hess may be null.
+ *
+ * mesh [B*N, 2] is the full move (mmpde_dmm_mesh_*'s output) and is relaxed in
+ * place: alpha_b * x + (1 - alpha_b) * xi in fp32 with every operation rounded
+ * by itself (no fma), so a float32 evaluation of that line on the host gives
+ * the same bits; rows of a trajectory with alpha_b == 1 are not touched, and
+ * alpha_b == 0 stores xi itself (what the line gives for finite x, up to the
+ * sign of a zero).  hess [B*N, 3] is mmpde_dmm_hess_io's hess_out.
+ *
+ * Every pointer of mmpde_dmm_relax_io is nullable (io itself too, with floor
+ * <= 0), except that floor > 0 needs alpha_out (the step reaches the relax
+ * kernel through it) and detmin_out / folds_out need det_out; lam_out and
+ * det_out need hess.  det_out is det(I + alpha_b Hess phi) at every node,
+ * detmin_out / folds_out its reductions as in mmpde_dmm_hess_io.  All outputs
+ * are written (guarded_total: added to) by the call itself in stream order and
+ * in a fixed order: no memset, no synchronisation, capturable, repeatable.
+ * Refused before any launch: null or misaligned pointers, alpha_max outside
+ * [0, 1], floor >= 1, NaN for either.
+ * Added without a version step: a library reporting 12302 may or may not
+ * export this symbol; look it up before calling. */
+typedef struct {
+    float *alpha_out;       /* [B]: the step taken */
+    float *lam_out;         /* [B]: min_n lambda_n (NaN if any is) */
+    float *det_out;         /* [B*N]: det(I + alpha_b Hess phi) */
+    float *detmin_out;      /* [B]: min of det_out over the trajectory (NaN if any is) */
+    int32_t *folds_out;     /* [B]: nodes with !(det_out > 0), NaN included */
+    int32_t *guarded_total; /* [B]: += (alpha_b < alpha_max); never reset by the call */
+} mmpde_dmm_relax_io;
+int mmpde_dmm_mesh_relax(float *mesh /*[B*N,2] in place*/, const float *xi /*[N,2]*/,
+                         const float *hess /*[B*N,3] or NULL when floor <= 0*/,
+                         int64_t batches, int64_t n_per, float alpha_max, float floor,
+                         const mmpde_dmm_relax_io *io, mmpde_stream_t stream);
+
 /* DMM.forward (dmm_model.py:185-219) in two calls, for callers that need phi
  * itself (DMM evaluation, dmm_utils.py) rather than the moved mesh.
  * The branch alone: branch_out [B, L] (L = hd->latent) from u on the fixed

@@ -1111,6 +1111,151 @@ extern "C" int mmpde_dmm_mesh_array_hess(const float *u, const float *xi, int64_
 }
 
 // ---------------------------------------------------------------------------
+// The fold guard: the reference's relaxation x = alpha x + (1 - alpha) xi
+// (data_creator_2d.py:109-111,133-135, alpha = 1 there) with alpha chosen per
+// trajectory from Hess phi.  The relaxed map's Jacobian is I + alpha Hess phi,
+// whose smallest eigenvalue at a node is 1 + alpha lambda_n, lambda_n the smaller
+// eigenvalue of Hess phi: on the way from alpha = 0 (the fixed grid) the first
+// node folds when 1 + alpha min_n lambda_n reaches 0, so the largest step that
+// keeps every eigenvalue of dx/dxi at or above a floor delta is
+//     alpha_b = min(alpha_max, (1 - delta) / (-min_n lambda_n)).
+// ---------------------------------------------------------------------------
+namespace {
+
+// lam[b] = min_n lambda_n (NaN if any lambda_n is), lambda_n = (h11 + h22) / 2 -
+// sqrt(((h11 - h22) / 2)^2 + h12^2), every operation rounded by itself (no fma:
+// a float32 evaluation on the host gives the same bits); alpha[b] as above
+// (floor <= 0: alpha_max; floor > 0 and lam NaN: 0); guarded_total[b] += alpha[b] < alpha_max.
+// One block per trajectory, the fixed order of det_reduce_kernel: every output
+// written, none read but guarded_total.  hess null: alpha alone (= alpha_max).
+__global__ __launch_bounds__(256) void relax_alpha_kernel(const float *__restrict__ hess,
+                                                          int64_t n_per, float alpha_max, float floor,
+                                                          float *__restrict__ lam_out,
+                                                          float *__restrict__ alpha_out,
+                                                          int32_t *__restrict__ guarded_total) {
+#pragma clang fp contract(off)  // every product and sum below rounds by itself
+    __shared__ float smin[4];
+    __shared__ int snan[4];
+    float mn = INFINITY;
+    int nan = 0;
+    if (hess) {
+        const float *h = hess + (int64_t)blockIdx.x * n_per * 3;
+#pragma unroll 4
+        for (int64_t i = threadIdx.x; i < n_per; i += 256) {
+            const float h11 = h[3 * i], h12 = h[3 * i + 1], h22 = h[3 * i + 2];
+            const float d = 0.5f * (h11 - h22);
+            const float r = sqrtf(d * d + h12 * h12);  // correctly rounded, as the division below
+            const float v = 0.5f * (h11 + h22) - r;
+            nan |= v != v;
+            mn = fminf(mn, v);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        mn = fminf(mn, __shfl_xor(mn, o, 64));
+        nan |= __shfl_xor(nan, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        smin[threadIdx.x >> 6] = mn;
+        snan[threadIdx.x >> 6] = nan;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        mn = fminf(fminf(smin[0], smin[1]), fminf(smin[2], smin[3]));
+        nan = snan[0] | snan[1] | snan[2] | snan[3];
+        float a = alpha_max;
+        if (nan) {
+            mn = __builtin_nanf("");
+            if (floor > 0.0f) a = 0.0f;
+        } else if (hess && floor > 0.0f &&!(1.0f + alpha_max * mn >= floor)) {
+            // 1 + alpha_max lam < floor < 1: lam < 0 and alpha_max > 0
+            a = fminf((1.0f - floor) / -mn, alpha_max);
+        }
+        if (lam_out) lam_out[blockIdx.x] = mn;
+        if (alpha_out) alpha_out[blockIdx.x] = a;
+        if (guarded_total) guarded_total[blockIdx.x] += a < alpha_max;
+    }
+}
+
+// mesh[b, i] = a mesh[b, i] + (1 - a) xi[i], a = alpha[b] (alpha null: alpha_max),
+// each product, the difference and the sum rounded by itself (the reference's
+// expression in float32).  a == 1 leaves the rows as they are, a == 0 stores xi
+// itself.  det (nullable, with hess): det(I + a Hess phi) by det_of on the
+// scaled entries.  blocks_per blocks of 256 rows per trajectory, so a is one
+// block-uniform load and the tail of a trajectory is cut by index.
+__global__ __launch_bounds__(256) void mesh_relax_kernel(float2 *__restrict__ mesh,
+                                                         const float2 *__restrict__ xi,
+                                                         const float *__restrict__ hess,
+                                                         const float *__restrict__ alpha,
+                                                         float alpha_max, int64_t n_per,
+                                                         int blocks_per, float *__restrict__ det) {
+#pragma clang fp contract(off)  // every product and sum below rounds by itself
+    const int b = blockIdx.x / blocks_per;
+    const float a = alpha ? alpha[b] : alpha_max;
+    if (a == 1.0f && !det) return;
+    const int64_t i = (int64_t)(blockIdx.x - b * blocks_per) * 256 + threadIdx.x;
+    if (i >= n_per) return;
+    const int64_t row = (int64_t)b * n_per + i;
+    if (a != 1.0f) {
+        const float2 g = xi[i];
+        float2 x = g;
+        if (a != 0.0f) {
+            const float2 m = mesh[row];
+            const float c = 1.0f - a;
+            x.x = a * m.x + c * g.x;
+            x.y = a * m.y + c * g.y;
+        }
+        mesh[row] = x;
+    }
+    if (det) {
+        const float *h = hess + 3 * row;
+        det[row] = det_of(a * h[0], a * h[1], a * h[2]);
+    }
+}
+
+inline bool al_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+}  // namespace
+
+extern "C" int mmpde_dmm_mesh_relax(float *mesh, const float *xi, const float *hess, int64_t batches,
+                                    int64_t n_per, float alpha_max, float floor,
+                                    const mmpde_dmm_relax_io *io, mmpde_stream_t stream) {
+    static const mmpde_dmm_relax_io none = {};
+    if (!io) io = &none;
+    MMPDE_REQUIRE(mesh && xi && al_to(mesh, 8) && al_to(xi, 8) && al_to(hess, 4));
+    MMPDE_REQUIRE(batches > 0 && n_per > 0);
+    MMPDE_REQUIRE(alpha_max >= 0.0f && alpha_max <= 1.0f && floor < 1.0f);  // NaN fails either
+    const bool guard = floor > 0.0f;
+    // lam and det are functions of Hess phi; the guard's alpha reaches the relax
+    // kernel through alpha_out, the reductions read det_out
+    MMPDE_REQUIRE(hess || !(guard || io->lam_out || io->det_out));
+    MMPDE_REQUIRE(!guard || io->alpha_out);
+    MMPDE_REQUIRE(io->det_out || !(io->detmin_out || io->folds_out));
+    MMPDE_REQUIRE(al_to(io->alpha_out, 4) && al_to(io->lam_out, 4) && al_to(io->det_out, 4) &&
+                  al_to(io->detmin_out, 4) && al_to(io->folds_out, 4) && al_to(io->guarded_total, 4));
+    const int64_t blocks_per = ceil_div(n_per, 256);
+    MMPDE_REQUIRE(batches <= INT32_MAX / blocks_per);
+    hipStream_t st = as_stream(stream);
+    if (hess || io->alpha_out) {
+        hipLaunchKernelGGL(relax_alpha_kernel, dim3((unsigned)batches), dim3(256), 0, st, hess, n_per,
+                           alpha_max, floor, io->lam_out, io->alpha_out, io->guarded_total);
+        MMPDE_RET_LAUNCH();
+    }
+    if (guard || alpha_max != 1.0f || io->det_out) {
+        hipLaunchKernelGGL(mesh_relax_kernel, dim3((unsigned)(batches * blocks_per)), dim3(256), 0, st,
+                           (float2 *)mesh, (const float2 *)xi, hess, guard ? io->alpha_out : nullptr,
+                           alpha_max, n_per, (int)blocks_per, io->det_out);
+        MMPDE_RET_LAUNCH();
+    }
+    if (io->detmin_out || io->folds_out) {
+        hipLaunchKernelGGL(det_reduce_kernel, dim3((unsigned)batches), dim3(256), 0, st, io->det_out, n_per,
+                           io->detmin_out, io->folds_out, (int32_t *)nullptr);
+        MMPDE_RET_LAUNCH();
+    }
+    return MMPDE_OK;
+}
+
+// ---------------------------------------------------------------------------
 // DMM.forward pieces: the branch alone and phi itself (dmm_model.py:185-219)
 // ---------------------------------------------------------------------------
 extern "C" int mmpde_dmm_branch_graph(const float *u, const float *grid, int64_t batches, int64_t n_per,

@@ -92,6 +92,12 @@ class DmmHessIO(ctypes.Structure):
                                   "folds_out", "folds_total")]
 
 
+class DmmRelaxIO(ctypes.Structure):
+    """mmpde_dmm_relax_io: the outputs of mmpde_dmm_mesh_relax, all nullable."""
+    _fields_ = [(n, _P) for n in ("alpha_out", "lam_out", "det_out", "detmin_out", "folds_out",
+                                  "guarded_total")]
+
+
 class ItpMlp(ctypes.Structure):
     _fields_ = [(n, _P) for n in ("w0", "b0", "w1", "b1", "w2", "b2")]
 
@@ -199,6 +205,7 @@ _SIGS = {
     "mmpde_dmm_hess_workspace_bytes": (_I64, [_I64, _I64, _I, _I]),
     "mmpde_dmm_mesh_graph_hess": (_I, [_P, _P, _I64, _I64, _P, _I, _P, _P, _P, _P, _P, _P]),
     "mmpde_dmm_mesh_array_hess": (_I, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+    "mmpde_dmm_mesh_relax": (_I, [_P, _P, _P, _I64, _I64, _F, _F, _P, _P]),
     "mmpde_dmm_branch_graph": (_I, [_P, _P, _I64, _I64, _P, _I, _P, _P, _P, _P, _P]),
     "mmpde_dmm_branch_array": (_I, [_P, _I64, _P, _P, _P, _P, _P]),
     "mmpde_dmm_phi_workspace_bytes": (_I64, [_I64, _I64, _I, _I, _I]),
@@ -228,7 +235,13 @@ def lib():
         except OSError as e:  # pragma: no cover - depends on the box
             raise HipExtensionMissing(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in _SIGS.items():
-            f = getattr(h, name)
+            try:
+                f = getattr(h, name)
+            except AttributeError:
+                # an entry added without a version step (mmpde_dmm_mesh_relax in 12302)
+                raise HipExtensionMissing(
+                    f"{LIB_PATH} (ABI {h.mmpde_version()}) does not export {name}: it was built "
+                    f"from an older tree; rebuild it with __graft_entry__.build()") from None
             f.restype = res
             f.argtypes = args
         v = h.mmpde_version()

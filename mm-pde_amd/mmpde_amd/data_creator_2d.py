@@ -45,6 +45,14 @@ class GraphCreator_FS_2D(nn.Module):  # noqa: N801 - reference name
         # "scan" or "binned" (ops.radius_graph_nbr): how create_graph's moved-mesh
         # radius graph searches; the same tables either way
         self.radius_method = "scan"
+        # the relaxation that ends the reference's moving_mesh[_tri], x = alpha x +
+        # (1 - alpha) xi (data_creator_2d.py:109-111,133-135, alpha = 1 hard-coded
+        # there): mesh_alpha is that alpha; mesh_guard None, or a floor in (0, 1)
+        # for the smallest eigenvalue of dx/dxi: a trajectory whose move would
+        # fold is then moved only as far as keeps it (DMM.mesh_guarded; eval mode).
+        # At the defaults moving_mesh[_tri] is DMM.mesh, the same bits.
+        self.mesh_alpha = 1.0
+        self.mesh_guard = None
 
     # ------------------------------------------------------------------ grids
     def _is_array(self):
@@ -145,6 +153,12 @@ class GraphCreator_FS_2D(nn.Module):  # noqa: N801 - reference name
         return data, labels
 
     # ------------------------------------------------------------------ mesh
+    def _mesh(self, mesh_model, u, xi):
+        """DMM.mesh, or with mesh_alpha / mesh_guard set the relaxed / guarded mesh."""
+        if self.mesh_guard is None and self.mesh_alpha == 1.0:
+            return mesh_model.mesh(u, xi)
+        return mesh_model.mesh_guarded(u, xi, floor=self.mesh_guard, alpha=self.mesh_alpha)[0]
+
     def moving_mesh(self, u, mesh_model, n_grid_x, n_grid_y):
         """data_creator_2d.py:88-113 (Burgers, DMM array mode).  u [B, nx, ny].
         Returns (x1, x2), each [B*nx*ny, 1]."""
@@ -152,14 +166,14 @@ class GraphCreator_FS_2D(nn.Module):  # noqa: N801 - reference name
         if mx != n_grid_x or my != n_grid_y:   # data_creator_2d.py:102-103
             u = ops.resample_bilinear(u, mx, my)
         xi = self.xi_grid_xy(n_grid_x, n_grid_y, u.device)
-        mesh = mesh_model.mesh(u, xi)
+        mesh = self._mesh(mesh_model, u, xi)
         return mesh[:, 0:1], mesh[:, 1:2]
 
     def moving_mesh_tri(self, u, mesh_model, grid_x, grid_y):
         """data_creator_2d.py:115-137 (cylinder, DMM graph mode).  grid_x/grid_y are
         the fixed grid repeated per trajectory ([B, N]); all trajectories share it."""
         xi = torch.stack((grid_x[0], grid_y[0]), -1)
-        mesh = mesh_model.mesh(u, xi)
+        mesh = self._mesh(mesh_model, u, xi)
         return mesh[:, 0:1], mesh[:, 1:2]
 
     # ------------------------------------------------------------------ interpolation

@@ -517,3 +517,55 @@ class DMM(nn.Module):
                 L.ptr(u), L.ptr(xi), B, N, ctypes.byref(bp), ctypes.byref(hd), ctypes.byref(io),
                 L.ptr(workspace), L.ptr(out), st), "mmpde_dmm_mesh_array_hess")
         return out, hess_out, det_out, detmin, folds
+
+    # ----------------------------------------------------------------- the fold guard
+    def mesh_guarded(self, u: torch.Tensor, xi: torch.Tensor, floor: float | None = 0.1, alpha: float = 1.0,
+                     out: torch.Tensor | None = None, hess_out: torch.Tensor | None = None,
+                     det_out: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
+                     head_cache: torch.Tensor | None = None, hess_cache: torch.Tensor | None = None,
+                     nbr: torch.Tensor | None = None, folds_total: torch.Tensor | None = None,
+                     guarded_total: torch.Tensor | None = None, alpha_out: torch.Tensor | None = None,
+                     lam_out: torch.Tensor | None = None, detmin_out: torch.Tensor | None = None,
+                     folds_out: torch.Tensor | None = None, det_before_out: torch.Tensor | None = None,
+                     detmin_before_out: torch.Tensor | None = None,
+                     folds_before_out: torch.Tensor | None = None):
+        """mesh_hess(u, xi) followed by the reference's relaxation x = alpha x +
+        (1 - alpha) xi (data_creator_2d.py:109-111,133-135; alpha = 1 there) with
+        the step chosen per trajectory (ops.mesh_relax): a trajectory whose full
+        move leaves an eigenvalue of dx/dxi = I + alpha Hess phi below `floor` at
+        some node is moved only as far as keeps it at floor; the others move by
+        `alpha` (at alpha = 1 their rows are mesh()'s bit for bit).  floor is a
+        parameter in (0, 1) (0.1: a default, not a measured optimum); the
+        damping is uniform over a trajectory.  floor None: mesh() and the plain
+        relaxation by alpha, no Hessian.  Eval mode, no autograd.  Buffers as for
+        mesh_hess; workspace: mmpde_dmm_hess_workspace_bytes (floor None:
+        mmpde_dmm_workspace_bytes); guarded_total: a [B] int32 counter, +=
+        (alpha_b < alpha); the *_before_out buffers take mesh_hess's det, detmin
+        and folds of the full move.
+        Returns (mesh [B*N, 2], alpha_b [B], lam_b [B] = the smallest eigenvalue of
+        Hess phi per trajectory, hess [B*N, 3], det_after [B*N], detmin_after [B],
+        folds_after [B] int32, folds_before [B] int32); floor None: the last six
+        are None."""
+        if self.training:
+            raise NotImplementedError("mesh_guarded is eval-mode: call .eval()")
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"alpha {alpha}: the relaxation takes 0 <= alpha <= 1")
+        if floor is not None and not 0.0 < floor < 1.0:
+            raise ValueError(f"floor {floor}: None (no guard) or 0 < floor < 1")
+        B = u.shape[0]
+        with torch.no_grad():
+            if floor is None:
+                out = self.mesh(u, xi, out=out, workspace=workspace, head_cache=head_cache, nbr=nbr)
+                _, alpha_b, _, _, _ = ops.mesh_relax(out, xi, batches=B, alpha=alpha, alpha_out=alpha_out,
+                                                     guarded_total=guarded_total)
+                return out, alpha_b, None, None, None, None, None, None
+            out, hess, _, _, folds_before = self.mesh_hess(
+                u, xi, out=out, hess_out=hess_out, det_out=det_before_out, workspace=workspace,
+                head_cache=head_cache, hess_cache=hess_cache, nbr=nbr, folds_total=folds_total,
+                detmin_out=detmin_before_out, folds_out=folds_before_out)
+            if det_out is None:
+                det_out = torch.empty((out.shape[0],), dtype=torch.float32, device=out.device)
+            _, alpha_b, lam, detmin, folds = ops.mesh_relax(
+                out, xi, hess, batches=B, alpha=alpha, floor=floor, alpha_out=alpha_out, lam_out=lam_out,
+                det_out=det_out, detmin_out=detmin_out, folds_out=folds_out, guarded_total=guarded_total)
+        return out, alpha_b, lam, hess, det_out, detmin, folds, folds_before

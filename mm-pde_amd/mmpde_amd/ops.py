@@ -838,6 +838,68 @@ def itp_interp(src, vals, qry, idx, batches: int, packed: torch.Tensor, addend=N
     return out
 
 
+def mesh_relax(mesh: torch.Tensor, xi: torch.Tensor, hess: torch.Tensor | None = None, *, batches: int,
+               alpha: float = 1.0, floor: float | None = None, alpha_out=None, lam_out=None, det_out=None,
+               detmin_out=None, folds_out=None, guarded_total=None):
+    """The fold guard (mmpde_dmm_mesh_relax): the relaxation that ends the
+    reference's moving_mesh[_tri], x = alpha x + (1 - alpha) xi
+    (data_creator_2d.py:109-111,133-135), in place on mesh [batches * N, 2] (the
+    full move of DMM.mesh / mesh_hess) with xi [N, 2] the fixed grid.
+    floor None: every trajectory is relaxed by alpha.  floor in (0, 1): a
+    trajectory whose full move would leave an eigenvalue of dx/dxi = I + alpha
+    Hess phi below floor at some node is moved only as far as keeps it at floor,
+    alpha_b = (1 - floor) / (-lam_b), lam_b the smallest eigenvalue of hess
+    [batches * N, 3] (mesh_hess's) over the trajectory; a NaN in a trajectory's
+    hess gives alpha_b = 0.  Rows of trajectories with alpha_b == 1 keep their
+    bits.  guarded_total: a [batches] int32 counter, += (alpha_b < alpha).
+    Returns (mesh, alpha_b [batches], lam_b [batches], detmin [batches], folds
+    [batches] int32), the last two of det(I + alpha_b Hess phi) (det_out:
+    [batches * N], to keep it); lam_b, detmin and folds are None without hess.
+    No synchronisation; capturable."""
+    L.require_device(mesh, xi, hess)
+    if mesh.dtype != torch.float32 or not mesh.is_contiguous() or mesh.dim() != 2 or mesh.shape[1] != 2 \
+            or mesh.data_ptr() % 8:
+        raise ValueError("mesh must be a contiguous float32 [batches * N, 2] tensor (it is relaxed in place)")
+    xi = L.f32c(xi).reshape(-1, 2)
+    n, N = mesh.shape[0], xi.shape[0]
+    if batches < 1 or n != batches * N or n == 0:
+        raise ValueError("mesh rows must be batches copies of xi's")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha {alpha}: the relaxation takes 0 <= alpha <= 1")
+    if floor is not None and not 0.0 < floor < 1.0:
+        raise ValueError(f"floor {floor}: None (no guard) or 0 < floor < 1")
+    if hess is None:
+        if floor is not None:
+            raise ValueError("the guard (floor) needs hess")
+        if not (lam_out is None and det_out is None and detmin_out is None and folds_out is None):
+            raise ValueError("lam_out, det_out, detmin_out and folds_out need hess")
+    elif hess.dtype != torch.float32 or not hess.is_contiguous() or hess.numel() != 3 * n:
+        raise ValueError("hess must be a contiguous float32 [batches * N, 3] tensor")
+
+    def buf(t, shape, dtype, what):
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=mesh.device)
+        L.require_device(t)
+        if t.dtype != dtype or not t.is_contiguous() or t.numel() != torch.Size(shape).numel():
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)}")
+        return t
+
+    alpha_b = buf(alpha_out, (batches,), torch.float32, "alpha_out")
+    lam = det = detmin = folds = None
+    if hess is not None:
+        lam = buf(lam_out, (batches,), torch.float32, "lam_out")
+        det = buf(det_out, (n,), torch.float32, "det_out")
+        detmin = buf(detmin_out, (batches,), torch.float32, "detmin_out")
+        folds = buf(folds_out, (batches,), torch.int32, "folds_out")
+    if guarded_total is not None:
+        guarded_total = buf(guarded_total, (batches,), torch.int32, "guarded_total")
+    io = L.DmmRelaxIO(L.ptr(alpha_b), L.ptr(lam), L.ptr(det), L.ptr(detmin), L.ptr(folds), L.ptr(guarded_total))
+    L.check(L.lib().mmpde_dmm_mesh_relax(L.ptr(mesh), L.ptr(xi), L.ptr(hess), batches, N, float(alpha),
+                                         float(floor) if floor is not None else 0.0, ctypes.byref(io),
+                                         L.stream(mesh.device)), "mmpde_dmm_mesh_relax")
+    return mesh, alpha_b, lam, detmin, folds
+
+
 def reverse_adjacency(nbr: torch.Tensor, degree: torch.Tensor | None = None,
                       n_src: int | None = None, check: bool = True, slot_pos: bool = False):
     """Source-major view of a target-major table, for the source-side gradient of

@@ -32,7 +32,12 @@ Changing weights after construction needs a new engine.
 A DMM fed its own predictions can fold the mesh (det(dx/dxi) <= 0 at a node),
 after which the moved-mesh graph and the interpolation are built on tangled
 points.  ``mesh_check = True`` makes the DMM stage report that
-(``mesh_report()``); it corrects nothing.
+(``mesh_report()``) without changing the step.  ``mesh_guard = delta`` corrects
+it: a trajectory whose move would leave an eigenvalue of dx/dxi below delta at
+some node is moved only as far as keeps it at delta (the reference's
+relaxation x = alpha x + (1 - alpha) xi with alpha chosen per trajectory,
+``DMM.mesh_guarded``); trajectories that do not fold keep their mesh bit for
+bit.  The damping is uniform over a trajectory, and phi is not smoothed.
 """
 from __future__ import annotations
 
@@ -69,6 +74,15 @@ class MMPDERollout:
         # their bits.  Settable before the first step and before enable_graph.
         self.mesh_check = False
         gc = graph_creator
+        # the fold guard (DMM.mesh_guarded): mesh_alpha is the alpha of the
+        # reference's relaxation x = alpha x + (1 - alpha) xi (1: the full move);
+        # mesh_guard None, or the floor delta in (0, 1) of the smallest
+        # eigenvalue of dx/dxi, which a trajectory's move is cut back to keep
+        # (0.1 is DMM.mesh_guarded's default, not a measured optimum).  Read from
+        # the graph creator; settable like mesh_check.  mesh_guard implies the
+        # Hessian path of mesh_check.
+        self.mesh_guard = getattr(gc, "mesh_guard", None)
+        self.mesh_alpha = getattr(gc, "mesh_alpha", 1.0)
         self.grid = gc.uniform_grid(self.device).contiguous()           # [N, 2]
         self.N = N = self.grid.shape[0]
         self.n = n = batches * N
@@ -114,6 +128,9 @@ class MMPDERollout:
             self.hess_cache = None
             self.mesh_hess = self.mesh_det = self.mesh_detmin = None
             self.mesh_folds = self.mesh_folds_total = None
+            # the fold guard's [B] extras (mesh_guard / mesh_alpha), likewise
+            self.mesh_alpha_b = self.mesh_lam = self.mesh_guarded_total = None
+            self.mesh_det_after = self.mesh_detmin_after = self.mesh_folds_after = None
             # the moved-mesh graph from the 128 nearest of each xi point, the
             # kNN-30 query of the fixed grid from the 128 nearest xi points of
             # each grid point (exact: csrc/knn.hip knn_cand_kernel, full search
@@ -255,9 +272,39 @@ class MMPDERollout:
         self.mesh_folds = torch.zeros((self.B,), **i32)
         self.mesh_folds_total = torch.zeros((self.B,), **i32)
 
+    def _ensure_mesh_guard(self):
+        """The guard's buffers (once): the monitor's, when the guard is on, and
+        the per-trajectory step, eigenvalue, counts and the det after the guard."""
+        if self.mesh_guard is not None:
+            self._ensure_mesh_check()
+        if self.mesh_alpha_b is not None and (self.mesh_guard is None or self.mesh_lam is not None):
+            return
+        f32 = dict(dtype=torch.float32, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        if self.mesh_alpha_b is None:
+            self.mesh_alpha_b = torch.ones((self.B,), **f32)
+            self.mesh_guarded_total = torch.zeros((self.B,), **i32)
+        if self.mesh_guard is not None:
+            self.mesh_lam = torch.zeros((self.B,), **f32)
+            self.mesh_det_after = torch.empty((self.n,), **f32)
+            self.mesh_detmin_after = torch.empty((self.B,), **f32)
+            self.mesh_folds_after = torch.zeros((self.B,), **i32)
+
     def _st_main1(self, u):
         B = self.B
-        if self.mesh_check:
+        if self.mesh_guard is not None:
+            # the Hessian path, then the relaxation with the step chosen per
+            # trajectory, before anything reads the mesh
+            self._ensure_mesh_guard()
+            self.dmm.mesh_guarded(u, self.xi, floor=self.mesh_guard, alpha=self.mesh_alpha, out=self.mesh,
+                                  hess_out=self.mesh_hess, det_out=self.mesh_det_after,
+                                  workspace=self.ws_dmm_hess, head_cache=self.dmm_cache,
+                                  hess_cache=self.hess_cache, folds_total=self.mesh_folds_total,
+                                  guarded_total=self.mesh_guarded_total, alpha_out=self.mesh_alpha_b,
+                                  lam_out=self.mesh_lam, detmin_out=self.mesh_detmin_after,
+                                  folds_out=self.mesh_folds_after, det_before_out=self.mesh_det,
+                                  detmin_before_out=self.mesh_detmin, folds_before_out=self.mesh_folds)
+        elif self.mesh_check:
             # the same mesh bits, with Hess phi, det and the fold counts beside them
             self._ensure_mesh_check()
             self.dmm.mesh_hess(u, self.xi, out=self.mesh, hess_out=self.mesh_hess, det_out=self.mesh_det,
@@ -266,6 +313,10 @@ class MMPDERollout:
                                detmin_out=self.mesh_detmin, folds_out=self.mesh_folds)
         else:
             self.dmm.mesh(u, self.xi, out=self.mesh, workspace=self.ws_dmm, head_cache=self.dmm_cache)
+        if self.mesh_guard is None and self.mesh_alpha != 1.0:
+            # the plain relaxation (the monitor, when on, reports the full move)
+            self._ensure_mesh_guard()
+            ops.mesh_relax(self.mesh, self.xi, batches=B, alpha=self.mesh_alpha, alpha_out=self.mesh_alpha_b)
         self._rb = self._radius_binned()
         if self.knn_binned or self._rb:
             # one binning of the moved mesh for the kNN-30 query (side2) and the graph (main2)
@@ -366,6 +417,8 @@ class MMPDERollout:
             raise ValueError("graph replay records no per-kernel events; clear trace_hook")
         if self.moving_mesh and self.mesh_check:
             self._ensure_mesh_check()   # allocations and the K table stay out of the capture
+        if self.moving_mesh and (self.mesh_guard is not None or self.mesh_alpha != 1.0):
+            self._ensure_mesh_guard()
         self._g_u = torch.empty_like(u_like).contiguous()
         self._g_u.copy_(u_like)
         self._g_t = torch.zeros((1,), dtype=torch.float32, device=self.device)
@@ -510,12 +563,23 @@ class MMPDERollout:
         mesh is not a mesh there) and its smallest det, and the folded nodes
         summed over every checked step since construction.  The monitor only
         reports; the step does not change.  None before the first checked step.
-        Synchronises."""
+        With the fold guard on (mesh_guard) these describe the full move, before
+        the guard, and the record adds per trajectory the step taken (alpha),
+        the smallest eigenvalue of Hess phi (lam_min), the folded nodes and the
+        smallest det of the relaxed mesh (folds_after, detmin_after) and the
+        number of steps since construction on which the guard cut the move
+        (guarded_total).  Synchronises."""
         if not self.moving_mesh or self.hess_cache is None:
             return None
         torch.cuda.synchronize(self.device)
-        return {"folds": self.mesh_folds.tolist(), "detmin": self.mesh_detmin.tolist(),
-                "folds_total": self.mesh_folds_total.tolist()}
+        rep = {"folds": self.mesh_folds.tolist(), "detmin": self.mesh_detmin.tolist(),
+               "folds_total": self.mesh_folds_total.tolist()}
+        if self.mesh_guard is not None and self.mesh_lam is not None:
+            rep.update(alpha=self.mesh_alpha_b.tolist(), lam_min=self.mesh_lam.tolist(),
+                       folds_after=self.mesh_folds_after.tolist(),
+                       detmin_after=self.mesh_detmin_after.tolist(),
+                       guarded_total=self.mesh_guarded_total.tolist())
+        return rep
 
     def rollout(self, u0: torch.Tensor, start_step: int, n_steps: int):
         """Feed each prediction back as the next input; returns the final state."""
