@@ -1095,7 +1095,7 @@ __global__ __launch_bounds__(512, NODE_WPE) void gnn_node_kernel(NodeArgs p) {
 
 // ---------------------------------------------------------------------------
 // Embedding + layer 0's message_net_1 halves in one launch (gnn_2d.py:99-106,
-// 122-131, then the first GNN layer's projections): per 64-row tile
+// 122-131, then the first GNN layer's projections): per ROWS = 32-row tile
 //   z  = relu(BN1(W0 [u, x/Lx, y/Ly, t/tmax] + b0))        (VALU, K = 4)
 //   h0 = BN4(W3 z + b3)            (F16X3: fp16x3 MFMA, W3 split in-kernel; F32: exact fp32)
 //   a0, b0 = layer 0's message_net_1 node halves of h0      (F16X3 or fp32)
