@@ -71,7 +71,7 @@ __device__ __forceinline__ float wave_max(float v) {
 // across rows.  Every lane of the wave must be active (a DPP read of a
 // disabled lane is not defined).  The swaps' outputs with both operands v:
 // lane l's partner value (l ^ 16, l ^ 32) is output 0 in the upper row (half),
-// output 1 in the lower (as knn.hip's xor_lane).
+// output 1 in the lower (as knn_common.hpp's xor_lane).
 template <int CTRL>
 __device__ __forceinline__ uint32_t dpp_u(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);

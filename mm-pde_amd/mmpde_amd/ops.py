@@ -322,7 +322,7 @@ def knn_graph_moved(pos: torch.Tensor, xi: torch.Tensor, cand, batches: int, k: 
 RADIUS_METHODS = ("scan", "binned")
 # Trajectories of at least this many points get the rollout's moved-mesh radius
 # graph through cell bins even when the step does not build them anyway
-# (csrc/knn.hip radius_binned_kernel): the smallest measured size from which
+# (csrc/knn_bins.hip radius_binned_kernel): the smallest measured size from which
 # binning plus the binned search stayed below the index-order scan at every
 # larger size, in both repeats (profiles/radius_times.txt).
 RADIUS_BINNED_MIN_POINTS = 9216

@@ -45,6 +45,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .moved_search import MovedMeshSearch
 
 
 # default of MMPDERollout.priorities (set_priorities)
@@ -61,7 +62,6 @@ class MMPDERollout:
         self.device = torch.device(device)
         self.moving_mesh = moving_mesh
         self.trace_hook = None   # callable() -> _lib.GnnTrace | None, one per GNN forward
-        self._knn_used = {}      # kNN searches that used the candidate table in the last step
         # run the fixed-grid model beside the moving-mesh chain (False: one stream,
         # e.g. to time single kernels without a concurrent neighbour)
         self.overlap = True
@@ -94,15 +94,9 @@ class MMPDERollout:
         if gc.e not in ("knn", "radius"):
             raise ValueError(f"connect_edge {gc.e!r}: knn | radius")
         self.radius_graph = gc.e == "radius"
-        self.radius_r = gc.radius() if self.radius_graph else None
         self.nbr_u, self.deg_u = gc.fixed_graph(self.grid, batches)
         self.deg_m = None
-        # the moved-mesh radius graph through the mesh's cell bins
-        # (ops.radius_graph_nbr method="binned"; the same tables): None = whenever
-        # the step bins the mesh anyway (knn_binned) or N >=
-        # ops.RADIUS_BINNED_MIN_POINTS; True / False force it.  Settable before
-        # the first step.
-        self.radius_binned = None
+        self.search = None
         self.t = gc.time_grid()
         f32 = dict(dtype=torch.float32, device=self.device)
         self.out_u = torch.empty((n, 1), **f32)
@@ -131,60 +125,9 @@ class MMPDERollout:
             # the fold guard's [B] extras (mesh_guard / mesh_alpha), likewise
             self.mesh_alpha_b = self.mesh_lam = self.mesh_guarded_total = None
             self.mesh_det_after = self.mesh_detmin_after = self.mesh_folds_after = None
-            # the moved-mesh graph from the 128 nearest of each xi point, the
-            # kNN-30 query of the fixed grid from the 128 nearest xi points of
-            # each grid point (exact: csrc/knn.hip knn_cand_kernel, full search
-            # where its bound fails).  Burgers' grid is in 'ij' order and xi in
-            # 'xy' order, so the query table is built for the grid's own order.
-            # A radius graph has no kNN-n search: no graph table, skip threshold
-            # or policy role; the query tables are the same either way.
-            if self.radius_graph:
-                self.knn_cand = None
-                self.knn_cand_q = ops.knn_candidates(self.xi, ref=None if self.grid is self.xi else self.grid)
-            else:
-                self.knn_cand = ops.knn_candidates(self.xi)
-                self.knn_cand_q = (self.knn_cand if self.grid is self.xi
-                                   else ops.knn_candidates(self.xi, ref=self.grid))
-            # trajectories whose typical displacement exceeds these go straight
-            # to the full search (about half the lookups would fail; read once)
-            self.knn_skip = ops.knn_skip_threshold(self.xi, self.knn_cand, gc.n + 1, moved_queries=True)
-            self.knn_skip_q = ops.knn_skip_threshold(self.xi, self.knn_cand_q, 30, ref=self.grid)
-            nb = max(L.lib().mmpde_knn_graph_cand_scratch_bytes(batches, N), 1)
-            self.knn_scratch = torch.empty((nb,), dtype=torch.uint8, device=self.device)
-            # the kNN-30 query runs on side2 beside the graph: its own scratch
-            self.knn_scratch_q = torch.empty((nb,), dtype=torch.uint8, device=self.device)
-            # queries of the kNN-30 searches whose sorted fp64 distances hold an
-            # exact tie (sklearn's order unpinned there): cumulative, read by
-            # knn_query_ties()
-            self.knn_ties = torch.zeros((1,), dtype=torch.int32, device=self.device)
-            # per-step displacement record shared by both (ops.knn_moved_cells)
-            self.knn_cells = torch.empty((L.lib().mmpde_knn_moved_cells_bytes(batches) // 4,),
-                                         dtype=torch.float32, device=self.device)
-            if kind == "burgers":
-                # mode '1': kNN-30 of the moved mesh (near xi, 'xy' order) onto the
-                # fixed grid: a table of the 128 grid points nearest each xi point,
-                # and a displacement record of the unmoved grid (all zero)
-                # (rebuilt every step, which also zeroes its miss counters)
-                self.knn_cand_1 = ops.knn_candidates(self.grid, ref=self.xi)
-                self.knn_skip_1 = ops.knn_skip_threshold(self.grid, self.knn_cand_1, 30, ref=self.xi,
-                                                         moved_queries=True)
-                self.knn_cells_1 = torch.empty_like(self.knn_cells)
-                self.knn_scratch_1 = torch.empty((nb,), dtype=torch.uint8, device=self.device)
-            # table vs full search per role, from the share the table answered at
-            # an earlier step (ops.KnnTablePolicy: the cost model, no sync)
-            self.knn_policy = ops.KnnTablePolicy(
-                self.device, batches, N, (() if self.radius_graph else ("graph",)) + ("query",)
-                + (("query1",) if kind == "burgers" else ()))
-            # Without a candidate table (N > 4096) the per-step searches go
-            # through cell bins of the moved mesh instead of scanning the whole
-            # trajectory (ops.knn_bins; csrc/knn.hip knn_binned_kernel): the
-            # same tables.  Settable before the first step; with it on, the
-            # tables above are not consulted.
-            self.knn_binned = self.knn_cand_q is None and N >= ops.KNN_BINNED_MIN_POINTS
-            self.knn_bins = None     # the moved mesh's bins, rebuilt every step (main1)
-            self.knn_bins_1 = None   # burgers mode '1': the fixed grid's bins, built once
-            if self.knn_binned:
-                self._ensure_bins()
+            # the per-step neighbour searches on the moved mesh: their tables,
+            # bins, policy and the choice among them (moved_search.py)
+            self.search = MovedMeshSearch(kind, gc, self.xi, self.grid, self.grid_rep, batches)
             # the fixed-grid model depends on u only: it runs on a side stream,
             # with its own workspace, beside the moving-mesh chain
             self.ws_gnn_u = torch.empty_like(self.ws_gnn)
@@ -240,20 +183,6 @@ class MMPDERollout:
     def _st_side(self, u_flat, step_idx):
         nodes_u = self._nodes(u_flat, self.grid_rep, self.nbr_u, step_idx, self.deg_u)
         self.model(nodes_u, out=self.out_u, workspace=self.ws_gnn_u, trace=self._trace())
-
-    def _ensure_bins(self):
-        if self.knn_bins is None:
-            nb = L.lib().mmpde_knn_bins_bytes(self.B, self.N)
-            self.knn_bins = torch.empty((nb,), dtype=torch.uint8, device=self.device)
-        if self.kind == "burgers" and self.knn_binned and self.knn_bins_1 is None:
-            self.knn_bins_1 = ops.knn_bins(self.grid_rep, self.B)
-
-    def _radius_binned(self) -> bool:
-        if not self.radius_graph:
-            return False
-        if self.radius_binned is None:
-            return bool(self.knn_binned) or self.N >= ops.RADIUS_BINNED_MIN_POINTS
-        return bool(self.radius_binned)
 
     def _ensure_mesh_check(self):
         """The monitor's table and buffers (once): K = dJ/dxi of the fixed grid,
@@ -317,81 +246,25 @@ class MMPDERollout:
             # the plain relaxation (the monitor, when on, reports the full move)
             self._ensure_mesh_guard()
             ops.mesh_relax(self.mesh, self.xi, batches=B, alpha=self.mesh_alpha, alpha_out=self.mesh_alpha_b)
-        self._rb = self._radius_binned()
-        if self.knn_binned or self._rb:
-            # one binning of the moved mesh for the kNN-30 query (side2) and the graph (main2)
-            self._ensure_bins()
-            ops.knn_bins(self.mesh, B, out=self.knn_bins)
-        if self.knn_binned:
-            self._use_g = self._use_q = False
-            self._knn_used = {"graph": False, "query": False}
-            self._cells = None
-            return
-        pol = self.knn_policy
-        self._use_g = not self.radius_graph and pol.use_table("graph")
-        self._use_q = pol.use_table("query")
-        self._knn_used = {"graph": self._use_g, "query": self._use_q}
-        self._cells = ops.knn_moved_cells(self.mesh, self.xi, B, out=self.knn_cells) \
-            if self.knn_cand_q is not None and (self._use_g or self._use_q) else None
+        self.search.begin_step(self.mesh)
 
     def _st_side2(self, u):
         B, N = self.B, self.N
-        pol, cells, mesh = self.knn_policy, self._cells, self.mesh
-        if self.knn_binned:
-            idx2 = ops.knn_query(mesh, self.grid_rep, B, 30, ties=self.knn_ties, method="binned",
-                                 bins=self.knn_bins)
-        elif self._use_q:
-            idx2 = ops.knn_query_moved(mesh, self.grid_rep, self.xi, self.knn_cand_q, B, 30,
-                                       self.knn_scratch_q, ref=self.grid, cells=cells,
-                                       skip_above=self.knn_skip_q, ties=self.knn_ties)
-            if cells is not None:
-                pol.after_table("query", cells, 1)
-        else:
-            idx2 = ops.knn_query(mesh, self.grid_rep, B, 30, ties=self.knn_ties)
-        self.idx2 = idx2
+        self.idx2 = self.search.knn("query", self.mesh)
         if self.kind == "burgers":
             self._res = self.itp.res_cut(u.reshape(B, 1, self.s, self.s)).reshape(-1)
         else:
             self._res = self.itp.res_cut(u.reshape(B, N)).reshape(-1)
 
     def _st_main2(self, u_flat, step_idx):
-        B = self.B
-        pol, cells, mesh = self.knn_policy, self._cells, self.mesh
-        if self.radius_graph:   # torch_cluster default max_num_neighbors = 32
-            if self._rb:
-                nbr_m, self.deg_m = ops.radius_graph_nbr(mesh, B, self.radius_r, 32, method="binned",
-                                                         bins=self.knn_bins)
-            else:
-                nbr_m, self.deg_m = ops.radius_graph_nbr(mesh, B, self.radius_r, 32)
-        elif self.knn_binned:
-            nbr_m = ops.knn_graph_nbr(mesh, B, self.gc.n, method="binned", bins=self.knn_bins)
-        elif self._use_g:
-            nbr_m = ops.knn_graph_moved(mesh, self.xi, self.knn_cand, B, self.gc.n, self.knn_scratch,
-                                        cells=cells, skip_above=self.knn_skip)
-            if cells is not None:
-                pol.after_table("graph", cells, 0)
-        else:
-            nbr_m = ops.knn_graph_nbr(mesh, B, self.gc.n)
-        self.nbr_m = nbr_m
+        mesh = self.mesh
+        self.nbr_m, self.deg_m = self.search.graph(mesh)
         if self.kind == "burgers":
-            self._knn_used["query1"] = not self.knn_binned and pol.use_table("query1")
-            if self.knn_binned:
-                idx1 = ops.knn_query(self.grid_rep, mesh, B, 30, ties=self.knn_ties, method="binned",
-                                     bins=self.knn_bins_1)
-            elif self._knn_used["query1"]:
-                cells1 = ops.knn_moved_cells(self.grid_rep, self.grid, B, out=self.knn_cells_1)
-                idx1 = ops.knn_query_moved(self.grid_rep, mesh, self.grid, self.knn_cand_1, B, 30,
-                                           self.knn_scratch_1, ref=self.xi, cells=cells1,
-                                           skip_above=self.knn_skip_1, ties=self.knn_ties)
-                if self.knn_cand_1 is not None:
-                    pol.after_table("query1", cells1, 1)
-            else:
-                idx1 = ops.knn_query(self.grid_rep, mesh, B, 30, ties=self.knn_ties)
-            self.idx1 = idx1
-            u_m = ops.itp_interp(self.grid_rep, u_flat, mesh, idx1, B, self.itp.packed("1"))
+            self.idx1 = self.search.knn("query1", mesh)
+            u_m = ops.itp_interp(self.grid_rep, u_flat, mesh, self.idx1, self.B, self.itp.packed("1"))
         else:
             u_m = u_flat
-        nodes_m = self._nodes(u_m, mesh, nbr_m, step_idx, self.deg_m)
+        nodes_m = self._nodes(u_m, mesh, self.nbr_m, step_idx, self.deg_m)
         self.model_b(nodes_m, out=self.out_b, workspace=self.ws_gnn, trace=self._trace())
 
     def _st_final(self):
@@ -517,34 +390,27 @@ class MMPDERollout:
         cur.wait_stream(side2)
         return self._st_final().reshape(u.shape)
 
+    # The search object's flags and tables under the engine's names: knn_binned
+    # and radius_binned are settable before the first step and before enable_graph.
+    knn_binned = property(lambda self: self.search.knn_binned,
+                          lambda self, on: setattr(self.search, "knn_binned", on))
+    radius_binned = property(lambda self: self.search.radius_binned,
+                             lambda self, on: setattr(self.search, "radius_binned", on))
+    knn_cand = property(lambda self: self.search.cand["graph"])
+    knn_cand_q = property(lambda self: self.search.cand["query"])
+
     def knn_table_share(self):
         """(graph, query[, burgers mode-'1' query]): the share of the last step's
         moved-mesh kNN lookups the candidate tables answered (the rest went to
         the full search); None for a search the policy ran without the table
         that step (ops.KnnTablePolicy).  Diagnostics: synchronises the device."""
-        if not self.moving_mesh or self.knn_cand_q is None:
-            return None
-        torch.cuda.synchronize(self.device)
-        used = self._knn_used
-        s = ops.knn_table_share(self.knn_cells, self.B, self.N).mean(0).tolist()
-        s = [s[0] if used.get("graph") else None, s[1] if used.get("query") else None]
-        if self.kind == "burgers":
-            s.append(ops.knn_table_share(self.knn_cells_1, self.B, self.N)[:, 1].mean().item()
-                     if used.get("query1") else None)
-        return tuple(s)
+        return self.search.table_share() if self.moving_mesh else None
 
     def knn_modes(self):
-        """Per neighbour search of the step: 'binned' (knn_binned), else 'table',
-        'full' or 'probe' (ops.KnnTablePolicy); a radius graph's role is
-        'radius-binned' or 'radius' (radius_binned)."""
-        if not self.moving_mesh:
-            return {}
-        modes = {"graph": "radius-binned" if self._radius_binned() else "radius"} if self.radius_graph else {}
-        if self.knn_binned:
-            modes.update({r: "binned" for r in self.knn_policy.state})
-        else:
-            modes.update({r: self.knn_policy.mode(r) for r in self.knn_policy.state})
-        return modes
+        """Per neighbour search of the step: 'binned' (knn_binned), else 'table'
+        or 'full' (ops.KnnTablePolicy); a radius graph's role is 'radius-binned'
+        or 'radius' (radius_binned).  moved_search.choose."""
+        return self.search.modes() if self.moving_mesh else {}
 
     def knn_query_ties(self) -> int:
         """Queries of the kNN-30 searches (reference data_creator_2d.py:75-76)
@@ -552,10 +418,7 @@ class MMPDERollout:
         the first 30 or at rank 30: the only inputs on which sklearn's order (its
         KD-tree traversal) may differ from the engine's (distance, index) order,
         i.e. where parity with the reference is unpinned.  Synchronises."""
-        if not self.moving_mesh:
-            return 0
-        torch.cuda.synchronize(self.device)
-        return int(self.knn_ties.item())
+        return self.search.query_ties() if self.moving_mesh else 0
 
     def mesh_report(self):
         """The fold monitor's record (mesh_check = True): per trajectory, the

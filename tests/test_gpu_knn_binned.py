@@ -1,4 +1,5 @@
-"""The cell-binned exact kNN (knn_bin_kernel / knn_binned_kernel, csrc/knn.hip):
+"""The cell-binned exact kNN (the binning kernels, csrc/knn_bins.hip;
+knn_binned_kernel, csrc/knn.hip):
 ops.knn_graph_nbr / ops.knn_query with method="binned", and the rollout's
 knn_binned routing.
 

@@ -1,4 +1,4 @@
-"""The cell-binned radius graph (radius_binned_kernel, csrc/knn.hip):
+"""The cell-binned radius graph (radius_binned_kernel, csrc/knn_bins.hip):
 ops.radius_graph_nbr with method="binned".
 
 Bars: nbr and deg torch.equal to method="scan" on the same input and to the C

@@ -1,4 +1,4 @@
-"""Host side of the cell-binned kNN (csrc/knn.hip mmpde_knn_bin*): the sizing
+"""Host side of the cell-binned kNN (csrc/knn_bins.hip mmpde_knn_bin*): the sizing
 helpers are pure host arithmetic and the bindings know the new entry points.
 No GPU."""
 import ctypes

@@ -1,4 +1,4 @@
-"""Host side of the cell-binned radius graph (csrc/knn.hip
+"""Host side of the cell-binned radius graph (csrc/knn_bins.hip
 mmpde_radius_graph_binned): the bindings know the entry point, and every
 refused argument is refused before any launch.  No GPU."""
 import ctypes
