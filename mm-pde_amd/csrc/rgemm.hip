@@ -219,6 +219,12 @@ __global__ __launch_bounds__(256, KH == 128 ? 1 : 2) void rgemm_ws_kernel(mmpde_
     const int ns = XS ? g.ns[p] : 0;
     const float *xs = g.xs;
     const int64_t ldxs = g.ldxs;
+    // columns of the small segment past this part's ns re-read its last one; a
+    // part without one (ns = 0 beside a part with ns > 0) reads column 0
+    const int xe1 = max(min(1, ns - 1), 0), xe2 = max(min(2, ns - 1), 0), xe3 = max(min(3, ns - 1), 0);
+    // all-ones / zero words (workgroup-uniform): the re-read columns are staged
+    // as zeros -- a product with xw[e] = 0 would let a NaN or Inf of theirs through
+    const int xm0 = ns > 0 ? -1 : 0, xm1 = ns > 1 ? -1 : 0, xm2 = ns > 2 ? -1 : 0, xm3 = ns > 3 ? -1 : 0;
     float4 stg[PER];
     float4 sxs;
     auto fetch = [&](int64_t tile) {
@@ -234,7 +240,7 @@ __global__ __launch_bounds__(256, KH == 128 ? 1 : 2) void rgemm_ws_kernel(mmpde_
         }
         if (XS && tid < 32) {
             const float *xr = xs + min(tile * 32 + tid, m - 1) * ldxs;
-            sxs = make_float4(xr[0], xr[min(1, ns - 1)], xr[min(2, ns - 1)], xr[min(3, ns - 1)]);
+            sxs = make_float4(xr[0], xr[xe1], xr[xe2], xr[xe3]);
         }
     };
     auto stash = [&](float *buf) {
@@ -244,7 +250,10 @@ __global__ __launch_bounds__(256, KH == 128 ? 1 : 2) void rgemm_ws_kernel(mmpde_
             const int r = f / (KH / 2), rem = f % (KH / 2), hh = rem / (KH / 4), q = rem % (KH / 4);
             *(float4 *)(buf + r * PITCH + hh * KH + 4 * q) = stg[u];
         }
-        if (XS && tid < 32) *(float4 *)(buf + tid * PITCH + 2 * KH) = sxs;
+        if (XS && tid < 32)
+            *(float4 *)(buf + tid * PITCH + 2 * KH) =
+                make_float4(__int_as_float(__float_as_int(sxs.x) & xm0), __int_as_float(__float_as_int(sxs.y) & xm1),
+                            __int_as_float(__float_as_int(sxs.z) & xm2), __int_as_float(__float_as_int(sxs.w) & xm3));
     };
     // epilogue constants of this lane's column
     const float bias = active && g.bias[p] ? g.bias[p][colc] : 0.0f;
@@ -306,7 +315,7 @@ __global__ __launch_bounds__(256, KH == 128 ? 1 : 2) void rgemm_ws_kernel(mmpde_
                     float y = d[r] + bias;
                     if (XS) {
                         const float4 x4 = *(const float4 *)(xt[cur] + rr * PITCH + 2 * KH);
-                        y = fmaf(x4.x, xw[0], y);   // xw[e] = 0 for e >= ns
+                        y = fmaf(x4.x, xw[0], y);   // staged 0 and xw[e] = 0 for e >= ns
                         y = fmaf(x4.y, xw[1], y);
                         y = fmaf(x4.z, xw[2], y);
                         y = fmaf(x4.w, xw[3], y);
