@@ -937,6 +937,76 @@ int mmpde_softmax_interp_grad(const float *pts, int64_t n_pts, int64_t pts_sets,
                               int64_t val_sets, const float *qry, int64_t n_q, float scale,
                               const float *grad_out, float *grad_qry, mmpde_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Mesh quality of a moved mesh (reference mesh/dmm_utils.py:1162-1284,
+ * evaluate_tri / evaluate), batched and per trajectory
+ * ---------------------------------------------------------------------- */
+
+/* The monitor function on the n x n unit lattice, flat 'xy' order (point
+ * i n + j = (x_j, y_i), dmm_utils.py:241-243), for B trajectories:
+ *     alpha[b] = sum sqrt(ux^2 + uy^2) / (n - 1)^2
+ *     m[b]     = 1 + sqrt(ux^2 + uy^2) / (0.01 alpha[b])     (dmm_utils.py:209-210)
+ *     rhs[b]   = sum m[b] / (n - 1)^2
+ * _array: u [B, n, n]; ux, uy = forward differences along the first / second
+ * axis times n - 1, the last row / column repeated (dmm_utils.py:215-225 and
+ * :36-37).  _grad: grad [B, n*n, 2] = (ux, uy) already on the lattice (point
+ * data: mmpde_softmax_interp_grad with the fixed grid as one point set, B value
+ * sets, the lattice repeated B times as queries, scale sqrt(N), grad_out = 1;
+ * dmm_utils.py:128-139).  m_out [B, n, n], alpha_out [B], rhs_out [B].  One
+ * workgroup per trajectory, sums in a fixed order (no atomics): the same bits on
+ * every run and for every B.  A constant field has alpha = 0 and gives NaN, as
+ * the reference does.  Refused before any launch: null pointers, B < 1, n < 2,
+ * n > MMPDE_MESH_QUALITY_MAX_N. */
+#define MMPDE_MESH_QUALITY_MAX_N 256
+int mmpde_mesh_monitor_array(const float *u, int64_t batches, int n, float *m_out, float *alpha_out,
+                             float *rhs_out, mmpde_stream_t stream);
+int mmpde_mesh_monitor_grad(const float *grad, int64_t batches, int n, float *m_out, float *alpha_out,
+                            float *rhs_out, mmpde_stream_t stream);
+
+/* Cell quality.  mesh [B*N, 2] the moved mesh, xi [N, 2] the fixed grid, cells
+ * [C, 4] int32 (16-B aligned) the cells as LOCAL node indices, m [B, n, n] the
+ * monitor field above.  Per trajectory and cell:
+ *   arity 4, vertices (bl, br, tl, tr) as dmm_utils.py:1264-1267: area =
+ *     |bl - tr| |br - tl| / 2 (the reference's product of the diagonals,
+ *     :1269-1272, which is not the true area of a general quadrilateral), centre
+ *     = mean of the four (:1273), signed area = (tr - bl) x (tl - br) / 2;
+ *   arity 3 (the fourth column is not read): area = |cross| / 2, centroid = mean
+ *     of the three (dmm_utils.py:1192-1198), signed area = cross / 2, cross =
+ *     (v1 - v0) x (v2 - v0);
+ *   mg = m(centre) area, m(centre) the reference's `interpolate`
+ *     (dmm_utils.py:233-249): softmax weights of -n |p - centre| over all n^2
+ *     lattice points p (coordinates float(i) / float(n - 1)), no window.
+ * Outputs, per trajectory, every pointer nullable:
+ *   mean, std (unbiased, as torch.std; two passes), range = max - min of mg over
+ *     the cells (dmm_utils.py:1228-1230, :1280-1282); NaN if any mg is;
+ *   inverted: cells whose signed area, with the sign that makes the same cell of
+ *     xi positive, is <= 0 or NaN;
+ *   area_ratio_min: min over the cells of signed moved area / signed area of the
+ *     same cell of xi (NaN if any ratio is);
+ *   inverted_total: inverted added to it; never reset by the call;
+ *   mg [B, C]: the per-cell values; when null they go to workspace, >=
+ *     mmpde_mesh_quality_workspace_bytes(B, C) = 4 B C rounded up to 16 bytes.
+ * A trajectory's outputs depend on its own rows only, in a fixed order: the same
+ * bits for every B and on every run; no memset, no synchronisation, capturable.
+ * Refused before any launch (MMPDE_ERR_INVALID_ARG): null mesh, xi, cells, m or
+ * io, null mg and workspace together, arity not 3 or 4, C < 1, n < 2, n >
+ * MMPDE_MESH_QUALITY_MAX_N, N < arity, B < 1 or > 65535.  Cell indices are
+ * clamped into [0, N) on the device, not checked: validate the table where it
+ * is built. */
+typedef struct {
+    float *mean;             /* [B] */
+    float *std;              /* [B] */
+    float *range;            /* [B] */
+    int32_t *inverted;       /* [B] */
+    float *area_ratio_min;   /* [B] */
+    int32_t *inverted_total; /* [B]: += inverted */
+    float *mg;               /* [B, C] */
+} mmpde_mesh_quality_io;
+int64_t mmpde_mesh_quality_workspace_bytes(int64_t batches, int64_t n_cells);
+int mmpde_mesh_quality(const float *mesh, const float *xi, int64_t batches, int64_t n_per,
+                       const int32_t *cells, int64_t n_cells, int arity, const float *m, int n,
+                       const mmpde_mesh_quality_io *io, void *workspace, mmpde_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,12 @@ class DmmRelaxIO(ctypes.Structure):
                                   "guarded_total")]
 
 
+class MeshQualityIO(ctypes.Structure):
+    """mmpde_mesh_quality_io: the outputs of mmpde_mesh_quality, all nullable."""
+    _fields_ = [(n, _P) for n in ("mean", "std", "range", "inverted", "area_ratio_min", "inverted_total",
+                                  "mg")]
+
+
 class ItpMlp(ctypes.Structure):
     _fields_ = [(n, _P) for n in ("w0", "b0", "w1", "b1", "w2", "b2")]
 
@@ -216,6 +222,10 @@ _SIGS = {
     "mmpde_itp_interp_ex": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
     "mmpde_softmax_interp": (_I, [_P, _I64, _I64, _P, _I64, _P, _I64, _F, _P, _P]),
     "mmpde_softmax_interp_grad": (_I, [_P, _I64, _I64, _P, _I64, _P, _I64, _F, _P, _P, _P]),
+    "mmpde_mesh_monitor_array": (_I, [_P, _I64, _I, _P, _P, _P, _P]),
+    "mmpde_mesh_monitor_grad": (_I, [_P, _I64, _I, _P, _P, _P, _P]),
+    "mmpde_mesh_quality_workspace_bytes": (_I64, [_I64, _I64]),
+    "mmpde_mesh_quality": (_I, [_P, _P, _I64, _I64, _P, _I64, _I, _P, _I, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -238,7 +248,7 @@ def lib():
             try:
                 f = getattr(h, name)
             except AttributeError:
-                # an entry added without a version step (mmpde_dmm_mesh_relax in 12302)
+                # an entry added without a version step (mmpde_dmm_mesh_relax, mmpde_mesh_quality in 12302)
                 raise HipExtensionMissing(
                     f"{LIB_PATH} (ABI {h.mmpde_version()}) does not export {name}: it was built "
                     f"from an older tree; rebuild it with __graft_entry__.build()") from None

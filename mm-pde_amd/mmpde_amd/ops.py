@@ -5,7 +5,9 @@ returns new device tensors; nothing here synchronises or falls back to CPU.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
+import math
 
 import os
 
@@ -898,6 +900,210 @@ def mesh_relax(mesh: torch.Tensor, xi: torch.Tensor, hess: torch.Tensor | None =
                                          float(floor) if floor is not None else 0.0, ctypes.byref(io),
                                          L.stream(mesh.device)), "mmpde_dmm_mesh_relax")
     return mesh, alpha_b, lam, detmin, folds
+
+
+# --------------------------------------------------------------------------- mesh quality
+MESH_QUALITY_MAX_N = 256   # include/mmpde_hip.h MMPDE_MESH_QUALITY_MAX_N
+
+MeshQuality = collections.namedtuple(
+    "MeshQuality", ("mean", "std", "range", "inverted", "area_ratio_min", "mg"))
+MeshQuality.__doc__ = """ops.mesh_quality's per-trajectory result: mean, std (unbiased) and range (max - min)
+of mg = monitor at the cell centre x cell area over the cells, the number of
+inverted cells (int32), the smallest signed moved area / fixed-grid area, all
+[batches]; mg [batches, C] or None."""
+
+
+def mesh_cells_lattice(s: int) -> torch.Tensor:
+    """The (s - 1)^2 quadrilaterals of the s x s lattice in flat 'xy' order, as
+    the reference slices them (dmm_utils.py:1264-1267): [(s - 1)^2, 4] int32 (CPU)
+    with columns (bl, br, tl, tr) = nodes (i, j), (i + 1, j), (i, j + 1),
+    (i + 1, j + 1) of x.reshape(s, s), cell i (s - 1) + j."""
+    if s < 2:
+        raise ValueError(f"a lattice of {s} x {s} points has no cells")
+    idx = torch.arange(s * s, dtype=torch.int32).reshape(s, s)
+    cols = (idx[:-1, :-1], idx[1:, :-1], idx[:-1, 1:], idx[1:, 1:])
+    return torch.stack([c.reshape(-1) for c in cols], dim=1).contiguous()
+
+
+def mesh_cells_delaunay(grid: torch.Tensor) -> torch.Tensor:
+    """The Delaunay triangles of the fixed grid [N, 2] (scipy, on the host, as
+    the reference's evaluate_tri, dmm_utils.py:1174-1178): [T, 3] int32 (CPU),
+    every triangle with its last two vertices swapped where needed so that
+    (v1 - v0) x (v2 - v0) > 0 on the grid; indices checked to lie in [0, N)."""
+    import numpy as np
+    from scipy.spatial import Delaunay
+
+    pts = grid.detach().cpu().numpy().astype(np.float64).reshape(-1, 2)
+    tris = np.asarray(Delaunay(pts).simplices).astype(np.int64)
+    if tris.ndim != 2 or tris.shape[1] != 3 or tris.shape[0] < 1:
+        raise ValueError("the grid has no Delaunay triangles")
+    if tris.min() < 0 or tris.max() >= pts.shape[0]:
+        raise ValueError("Delaunay returned an index outside the grid")
+    v = pts[tris]
+    e1, e2 = v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]
+    cross = e1[:, 0] * e2[:, 1] - e2[:, 0] * e1[:, 1]
+    flip = cross < 0
+    tris[flip] = tris[flip][:, [0, 2, 1]]
+    return torch.from_numpy(tris.astype(np.int32)).contiguous()
+
+
+def _cell_table(cells: torch.Tensor, n_per: int, device) -> tuple[torch.Tensor, int]:
+    """cells [C, 3 | 4] -> the device table [C, 4] int32 mmpde_mesh_quality reads
+    (a triangle's fourth column repeats its third) and the arity; indices
+    validated on the host (the kernels only clamp them)."""
+    if cells.dim() != 2 or cells.shape[1] not in (3, 4) or cells.shape[0] < 1:
+        raise ValueError("cells must be [C, 3] (triangles) or [C, 4] (quadrilaterals), C >= 1")
+    arity = cells.shape[1]
+    c = cells.detach().cpu().to(torch.int64)
+    if int(c.min()) < 0 or int(c.max()) >= n_per:
+        raise ValueError(f"cell indices must lie in [0, {n_per})")
+    if arity == 3:
+        c = torch.cat((c, c[:, 2:]), dim=1)
+    return c.to(torch.int32).contiguous().to(device), arity
+
+
+class MeshCells:
+    """A validated cell table on the device (ops.mesh_quality builds one from a
+    [C, 3 | 4] index tensor; build it once to reuse it across calls)."""
+
+    def __init__(self, cells: torch.Tensor, n_per: int, device):
+        self.table, self.arity = _cell_table(cells, n_per, device)
+        self.n_per = n_per
+        self.n_cells = self.table.shape[0]
+
+
+def _monitor_lattice(n: int, batches: int, device):
+    """The unit lattice repeated per trajectory [B n^2, 2] and the ones [B n^2]
+    that mmpde_softmax_interp_grad takes as queries and grad_out."""
+    from .dmm_train import unit_lattice
+
+    return (unit_lattice(n, device).repeat(batches, 1).contiguous(),
+            torch.ones((batches * n * n,), dtype=torch.float32, device=device))
+
+
+def mesh_monitor(u: torch.Tensor, grid: torch.Tensor | None = None, *, out=None, scratch=None):
+    """The monitor function of the reference's evaluate / evaluate_tri on the
+    n x n unit lattice (flat 'xy' order, dmm_train.unit_lattice), per trajectory:
+    alpha = sum |grad u| / (n - 1)^2, m = 1 + |grad u| / (0.01 alpha), rhs = sum m
+    / (n - 1)^2 (dmm_utils.py:209-210, :1215-1217, :1248-1252).
+    grid None: array data u [B, s, s], n = s, forward differences times s - 1.
+    grid [N, 2]: point data u [B, N] on the fixed grid, n = floor(sqrt(N)), the
+    gradient of the softmax smoother of u at the lattice points
+    (mmpde_softmax_interp_grad, scale sqrt(N)).
+    Returns (m [B, n, n], alpha [B], rhs [B]).  A constant field has alpha = 0 and
+    gives NaN, as the reference does.  out: (m, alpha, rhs) to write into;
+    scratch: point data's (queries [B n^2, 2], ones [B n^2], grad [B n^2, 2]).
+    No synchronisation; with out and scratch given, no allocation (capturable)."""
+    L.require_device(u, grid)
+    u = L.f32c(u)
+    if grid is None:
+        if u.dim() != 3 or u.shape[1] != u.shape[2]:
+            raise ValueError("array data must be [B, s, s]")
+        B, n = u.shape[0], u.shape[1]
+    else:
+        grid = L.f32c(grid).reshape(-1, 2)
+        if u.dim() != 2 or u.shape[1] != grid.shape[0]:
+            raise ValueError("point data must be [B, N] on a grid [N, 2]")
+        B, N = u.shape
+        n = int(math.isqrt(N))
+    if not 2 <= n <= MESH_QUALITY_MAX_N:
+        raise ValueError(f"monitor lattice n = {n}: 2 <= n <= {MESH_QUALITY_MAX_N}")
+    f32 = dict(dtype=torch.float32, device=u.device)
+    if out is None:
+        out = (torch.empty((B, n, n), **f32), torch.empty((B,), **f32), torch.empty((B,), **f32))
+    m, alpha, rhs = out
+    for t, numel in ((m, B * n * n), (alpha, B), (rhs, B)):
+        L.require_device(t)
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel:
+            raise ValueError("out must be contiguous float32 (m [B, n, n], alpha [B], rhs [B])")
+    st = L.stream(u.device)
+    if grid is None:
+        L.check(L.lib().mmpde_mesh_monitor_array(L.ptr(u), B, n, L.ptr(m), L.ptr(alpha), L.ptr(rhs), st),
+                "mmpde_mesh_monitor_array")
+        return m, alpha, rhs
+    if scratch is None:
+        qry, ones = _monitor_lattice(n, B, u.device)
+        scratch = (qry, ones, torch.empty_like(qry))
+    qry, ones, g = scratch
+    if qry.shape != (B * n * n, 2) or ones.numel() != B * n * n or g.shape != qry.shape:
+        raise ValueError("scratch must be (queries [B n^2, 2], ones [B n^2], grad [B n^2, 2])")
+    L.check(L.lib().mmpde_softmax_interp_grad(L.ptr(grid), N, 1, L.ptr(u), B, L.ptr(qry), B * n * n,
+                                              float(math.sqrt(N)), L.ptr(ones), L.ptr(g), st),
+            "mmpde_softmax_interp_grad")
+    L.check(L.lib().mmpde_mesh_monitor_grad(L.ptr(g), B, n, L.ptr(m), L.ptr(alpha), L.ptr(rhs), st),
+            "mmpde_mesh_monitor_grad")
+    return m, alpha, rhs
+
+
+def mesh_quality(mesh: torch.Tensor, xi: torch.Tensor, cells, m: torch.Tensor, batches: int, *,
+                 mg: bool | torch.Tensor = False, inverted_total: torch.Tensor | None = None, out=None,
+                 workspace: torch.Tensor | None = None) -> MeshQuality:
+    """The equidistribution statistics and the inverted cells of a moved mesh
+    (mmpde_mesh_quality; reference dmm_utils.py:1162-1284, per trajectory and on
+    the device).  mesh [batches * N, 2], xi [N, 2] the fixed grid, cells a
+    [C, 4] (mesh_cells_lattice) or [C, 3] (mesh_cells_delaunay) index tensor or
+    a MeshCells, m [batches, n, n] from mesh_monitor.  Per cell mg = m(centre) x
+    area: a quadrilateral's area is the reference's product of the diagonals /
+    2, its centre the vertices' mean; a triangle's area |cross| / 2, its centre
+    the centroid; m(centre) the softmax smoother over all n^2 lattice points
+    with scale n.  A cell is inverted when its signed area, oriented so that the
+    fixed-grid cell is positive, is <= 0 or NaN.  A trajectory's results do not
+    depend on the other trajectories.
+    mg: True (or a [batches, C] tensor) to keep the per-cell values;
+    inverted_total: a [batches] int32 counter, += inverted; out: (mean, std,
+    range, inverted, area_ratio_min) to write into.  No synchronisation; with a
+    MeshCells, out and workspace (or mg) given, no allocation (capturable)."""
+    L.require_device(mesh, xi, m)
+    mesh = L.f32c(mesh).reshape(-1, 2)
+    xi = L.f32c(xi).reshape(-1, 2)
+    m = L.f32c(m)
+    N = xi.shape[0]
+    if batches < 1 or mesh.shape[0] != batches * N or N == 0:
+        raise ValueError("mesh rows must be batches copies of xi's")
+    if m.dim() != 3 or m.shape[0] != batches or m.shape[1] != m.shape[2]:
+        raise ValueError("m must be [batches, n, n]")
+    n = m.shape[1]
+    if not isinstance(cells, MeshCells):
+        cells = MeshCells(cells, N, mesh.device)
+    if cells.n_per != N or cells.table.device != mesh.device:
+        raise ValueError("the cell table was built for another grid or device")
+    C = cells.n_cells
+    f32 = dict(dtype=torch.float32, device=mesh.device)
+    i32 = dict(dtype=torch.int32, device=mesh.device)
+    if out is None:
+        out = (torch.empty((batches,), **f32), torch.empty((batches,), **f32), torch.empty((batches,), **f32),
+               torch.empty((batches,), **i32), torch.empty((batches,), **f32))
+    for t, dt in zip(out, (torch.float32,) * 3 + (torch.int32, torch.float32)):
+        L.require_device(t)
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != batches:
+            raise ValueError("out must be contiguous [batches] tensors (float32; inverted int32)")
+    mean, std, rng, inverted, ratio = out
+    if inverted_total is not None:
+        L.require_device(inverted_total)
+        if inverted_total.dtype != torch.int32 or not inverted_total.is_contiguous() \
+                or inverted_total.numel() != batches:
+            raise ValueError("inverted_total must be a contiguous int32 [batches] tensor")
+    if mg is True:
+        mg = torch.empty((batches, C), **f32)
+    elif mg is False:
+        mg = None
+    if mg is not None:
+        L.require_device(mg)
+        if mg.dtype != torch.float32 or not mg.is_contiguous() or mg.numel() != batches * C:
+            raise ValueError("mg must be a contiguous float32 [batches, C] tensor")
+    else:
+        nb = L.lib().mmpde_mesh_quality_workspace_bytes(batches, C)
+        if workspace is None:
+            workspace = torch.empty((nb // 4,), **f32)
+        L.require_device(workspace)
+        if workspace.numel() * workspace.element_size() < nb or workspace.data_ptr() % 16:
+            raise ValueError(f"workspace must hold {nb} bytes, 16-B aligned")
+    io = L.MeshQualityIO(L.ptr(mean), L.ptr(std), L.ptr(rng), L.ptr(inverted), L.ptr(ratio),
+                         L.ptr(inverted_total), L.ptr(mg))
+    L.check(L.lib().mmpde_mesh_quality(L.ptr(mesh), L.ptr(xi), batches, N, L.ptr(cells.table), C, cells.arity,
+                                       L.ptr(m), n, ctypes.byref(io), L.ptr(workspace),
+                                       L.stream(mesh.device)), "mmpde_mesh_quality")
+    return MeshQuality(mean, std, rng, inverted, ratio, mg)
 
 
 def reverse_adjacency(nbr: torch.Tensor, degree: torch.Tensor | None = None,

@@ -38,8 +38,21 @@ some node is moved only as far as keeps it at delta (the reference's
 relaxation x = alpha x + (1 - alpha) xi with alpha chosen per trajectory,
 ``DMM.mesh_guarded``); trajectories that do not fold keep their mesh bit for
 bit.  The damping is uniform over a trajectory, and phi is not smoothed.
+
+Both judge the continuous map at the nodes.  ``mesh_quality = True`` adds the
+discrete view of the mesh the step used (after the guard / relaxation), per
+trajectory and on a side stream, without changing the step: the reference's
+equidistribution measure (evaluate / evaluate_tri, dmm_utils.py:1162-1284:
+monitor function at each moved cell's centre times the cell's area; mean, std
+and max - min over the cells) and the number of inverted cells (signed area
+against the same cell of the fixed grid), ``mesh_quality_report()``.  The cells
+are the lattice quadrilaterals (Burgers) or the fixed grid's Delaunay triangles
+(cylinder); the monitor lattice is the unit square, as in the reference.
 """
 from __future__ import annotations
+
+import math
+from types import SimpleNamespace
 
 import torch
 
@@ -83,6 +96,10 @@ class MMPDERollout:
         # Hessian path of mesh_check.
         self.mesh_guard = getattr(gc, "mesh_guard", None)
         self.mesh_alpha = getattr(gc, "mesh_alpha", 1.0)
+        # the mesh-quality stage (the mesh_quality property): its cell table,
+        # buffers and stream are built on the first such step (_ensure_mesh_quality)
+        self._mesh_quality = False
+        self.mesh_q = None
         self.grid = gc.uniform_grid(self.device).contiguous()           # [N, 2]
         self.N = N = self.grid.shape[0]
         self.n = n = batches * N
@@ -219,6 +236,66 @@ class MMPDERollout:
             self.mesh_detmin_after = torch.empty((self.B,), **f32)
             self.mesh_folds_after = torch.zeros((self.B,), **i32)
 
+    # mesh_quality: settable before the first step and before enable_graph, like
+    # mesh_check.  The step then also runs the monitor and cell-quality kernels on
+    # the final mesh (ops.mesh_monitor, ops.mesh_quality) on a side stream; they
+    # read u and self.mesh and write their own buffers only.
+    @property
+    def mesh_quality(self) -> bool:
+        return self._mesh_quality
+
+    @mesh_quality.setter
+    def mesh_quality(self, on) -> None:
+        on = bool(on)
+        if on:
+            if not self.moving_mesh:
+                raise ValueError("mesh_quality needs a moving mesh")
+            pde = self.gc.pde
+            if self.kind == "burgers" and (float(pde.Lx) != 1.0 or float(pde.Ly) != 1.0):
+                raise ValueError(f"mesh_quality: the monitor lattice is the unit square (dmm_utils.py:1238-1240), "
+                                 f"the domain is {pde.Lx} x {pde.Ly}")
+        if on != self._mesh_quality:
+            self._graphs = None   # the captured stages are those of the other setting
+        self._mesh_quality = on
+
+    def _ensure_mesh_quality(self):
+        """The quality stage's cell table, buffers and stream (once): the lattice
+        quadrilaterals (Burgers) or the fixed grid's Delaunay triangles (cylinder,
+        scipy on the host), the monitor field and the per-trajectory outputs."""
+        if self.mesh_q is not None:
+            return
+        B, N = self.B, self.N
+        f32 = dict(dtype=torch.float32, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        q = SimpleNamespace(steps=0)
+        if self.kind == "burgers":
+            q.cells = ops.MeshCells(ops.mesh_cells_lattice(self.s), N, self.device)
+            q.n = self.s
+            q.scratch = None
+        else:
+            q.cells = ops.MeshCells(ops.mesh_cells_delaunay(self.grid), N, self.device)
+            q.n = math.isqrt(N)
+            qry, ones = ops._monitor_lattice(q.n, B, self.device)
+            q.scratch = (qry, ones, torch.empty_like(qry))
+        q.m = torch.empty((B, q.n, q.n), **f32)
+        q.alpha, q.rhs = torch.empty((B,), **f32), torch.empty((B,), **f32)
+        q.mean, q.std, q.range = (torch.empty((B,), **f32) for _ in range(3))
+        q.inverted = torch.zeros((B,), **i32)
+        q.area_ratio_min = torch.empty((B,), **f32)
+        q.inverted_total = torch.zeros((B,), **i32)
+        q.ws = torch.empty((L.lib().mmpde_mesh_quality_workspace_bytes(B, q.cells.n_cells) // 4,), **f32)
+        q.stream = torch.cuda.Stream(self.device)
+        self.mesh_q = q
+
+    def _st_quality(self, u):
+        q = self.mesh_q
+        if self.kind == "burgers":
+            ops.mesh_monitor(u.reshape(self.B, self.s, self.s), out=(q.m, q.alpha, q.rhs))
+        else:
+            ops.mesh_monitor(u.reshape(self.B, self.N), self.grid, out=(q.m, q.alpha, q.rhs), scratch=q.scratch)
+        ops.mesh_quality(self.mesh, self.xi, q.cells, q.m, self.B, inverted_total=q.inverted_total,
+                         out=(q.mean, q.std, q.range, q.inverted, q.area_ratio_min), workspace=q.ws)
+
     def _st_main1(self, u):
         B = self.B
         if self.mesh_guard is not None:
@@ -292,6 +369,8 @@ class MMPDERollout:
             self._ensure_mesh_check()   # allocations and the K table stay out of the capture
         if self.moving_mesh and (self.mesh_guard is not None or self.mesh_alpha != 1.0):
             self._ensure_mesh_guard()
+        if self.moving_mesh and self._mesh_quality:
+            self._ensure_mesh_quality()   # the cell table, buffers and stream likewise
         self._g_u = torch.empty_like(u_like).contiguous()
         self._g_u.copy_(u_like)
         self._g_t = torch.zeros((1,), dtype=torch.float32, device=self.device)
@@ -316,6 +395,8 @@ class MMPDERollout:
         else:
             capture("side", cap if serial else self.side, lambda: self._st_side(u_flat, t))
             capture("main1", cap, lambda: self._st_main1(u))
+            if self._mesh_quality:
+                capture("quality", cap if serial else self.mesh_q.stream, lambda: self._st_quality(u))
             capture("side2", cap if serial else self.side2, lambda: self._st_side2(u))
             capture("main2", cap, lambda: self._st_main2(u_flat, t))
             self._g_out = capture("final", cap, self._st_final).reshape(u.shape)
@@ -335,20 +416,31 @@ class MMPDERollout:
             g["main"].replay()
             return self._g_out
         if self._graph_serial:
-            for name in ("side", "main1", "side2", "main2", "final"):
-                g[name].replay()
+            for name in ("side", "main1", "quality", "side2", "main2", "final"):
+                if name in g:
+                    g[name].replay()
+            if "quality" in g:
+                self.mesh_q.steps += 1
             return self._g_out
         cur = torch.cuda.current_stream(self.device)
         self.side.wait_stream(cur)
         with torch.cuda.stream(self.side):
             g["side"].replay()
         g["main1"].replay()
+        if "quality" in g:   # beside everything that follows: it only reads u and the mesh
+            sq = self.mesh_q.stream
+            sq.wait_stream(cur)
+            with torch.cuda.stream(sq):
+                g["quality"].replay()
+            self.mesh_q.steps += 1
         self.side2.wait_stream(cur)
         with torch.cuda.stream(self.side2):
             g["side2"].replay()
         g["main2"].replay()
         cur.wait_stream(self.side)
         cur.wait_stream(self.side2)
+        if "quality" in g:
+            cur.wait_stream(sq)   # the next step's DMM stage overwrites the mesh
         g["final"].replay()
         return self._g_out
 
@@ -375,6 +467,16 @@ class MMPDERollout:
             self._st_side(u_flat, step_idx)
         if main is cur:
             self._st_main1(u)
+        if self._mesh_quality:
+            # the mesh is final: the quality stage beside everything that follows
+            self._ensure_mesh_quality()
+            sq = self.mesh_q.stream if self.overlap else main
+            if sq is not main:
+                sq.wait_stream(main)
+            with torch.cuda.stream(sq):
+                u.record_stream(sq)
+                self._st_quality(u)
+            self.mesh_q.steps += 1
         side2 = self.side2 if self.overlap else cur
         side2.wait_stream(main)
         with torch.cuda.stream(side2):
@@ -388,6 +490,8 @@ class MMPDERollout:
             cur.wait_stream(main)
         cur.wait_stream(side)
         cur.wait_stream(side2)
+        if self._mesh_quality and sq is not cur:
+            cur.wait_stream(sq)   # the next step's DMM stage overwrites the mesh
         return self._st_final().reshape(u.shape)
 
     # The search object's flags and tables under the engine's names: knn_binned
@@ -443,6 +547,23 @@ class MMPDERollout:
                        detmin_after=self.mesh_detmin_after.tolist(),
                        guarded_total=self.mesh_guarded_total.tolist())
         return rep
+
+    def mesh_quality_report(self):
+        """The quality stage's record of the last step (mesh_quality = True), per
+        trajectory: mean, std and range (max - min) over the cells of the monitor
+        function at the moved cell's centre times the cell's area (the
+        reference's evaluate / evaluate_tri figures, for the mesh the step used),
+        the monitor's rhs and alpha, the number of inverted cells (signed area
+        <= 0 or NaN against the same cell of the fixed grid), the smallest signed
+        moved area / fixed area, and the inverted cells summed over every such
+        step since construction.  A constant u has alpha = 0 and NaN statistics,
+        as in the reference.  None before the first such step.  Synchronises."""
+        q = self.mesh_q
+        if q is None or q.steps == 0:
+            return None
+        torch.cuda.synchronize(self.device)
+        return {k: getattr(q, k).tolist() for k in ("mean", "std", "range", "rhs", "alpha", "inverted",
+                                                    "area_ratio_min", "inverted_total")}
 
     def rollout(self, u0: torch.Tensor, start_step: int, n_steps: int):
         """Feed each prediction back as the next input; returns the final state."""
