@@ -918,6 +918,64 @@ int mmpde_itp_interp_ex(const float *src, const float *vals, const float *qry, c
                         int64_t batches, int64_t n_src, int64_t n_qry, const void *packed,
                         const float *addend, const float *addend2, float *out, mmpde_stream_t stream);
 
+/* The same interpolation for any ItpNet the reference builds from
+ * --itpnet_node1/2 (interpolate.py:5-30: layers = [62] + hidden + [30]) within
+ * these limits: n_layers Linears, 1 <= n_layers <= MMPDE_ITP_MAX_LAYERS (0 to 4
+ * hidden layers and the output layer), widths[0] = 62, widths[n_layers] = 30,
+ * hidden widths 1 .. MMPDE_ITP_MAX_WIDTH; w[l] is torch's [widths[l+1],
+ * widths[l]] row-major weight, b[l] its [widths[l+1]] bias; tanh between the
+ * layers, none after the last.  The default 62 -> 128 -> 64 -> 30 is served by
+ * either family; mmpde_itp_interp(_ex) is the faster one for it.
+ * Added without a version step: a library reporting 12302 may or may not
+ * export these symbols; look them up before calling. */
+#define MMPDE_ITP_MAX_LAYERS 5
+#define MMPDE_ITP_MAX_WIDTH 256
+typedef struct {
+    int n_layers;
+    int widths[MMPDE_ITP_MAX_LAYERS + 1];
+    const float *w[MMPDE_ITP_MAX_LAYERS];
+    const float *b[MMPDE_ITP_MAX_LAYERS];
+} mmpde_itp_net;
+
+/* Bytes of the image mmpde_itp_net_pack writes for this shape (host arithmetic
+ * on n_layers and widths only; w and b are not read): every width padded to a
+ * multiple of 16, sum over the layers of P(out) * (P(in) + 1) floats with
+ * P(62) = 64.  0 for a null net or a shape outside the limits above. */
+int64_t mmpde_itp_net_pack_bytes(const mmpde_itp_net *net);
+/* Re-lay the weights and biases into the MFMA operand image of
+ * mmpde_itp_interp_net: every float of the first mmpde_itp_net_pack_bytes(net)
+ * bytes of packed is written, the zero padding included.  packed 16-byte
+ * aligned, packed_bytes >= mmpde_itp_net_pack_bytes(net). */
+int mmpde_itp_net_pack(const mmpde_itp_net *net, void *packed, int64_t packed_bytes,
+                       mmpde_stream_t stream);
+/* mmpde_itp_interp_ex with the packed image of mmpde_itp_net_pack: the same
+ * arrays (idx [B*Nq,30] LOCAL, clamped into [0, n_src) on the device), out =
+ * (addend + sum) + addend2, both nullable.  Of shape only n_layers and widths
+ * are read, on the host at the call: w and b may be null, and a captured launch
+ * holds no host pointer.  A query's result depends on its own inputs only: the
+ * same bits on every run, in any batch, at any n_qry.
+ * Launch geometry: query tile T (16 consecutive queries of one trajectory, the
+ * last of a trajectory partial; ceil(n_qry / 16) * batches tiles, trajectory
+ * major) is one wave's work.  Workgroups of MMPDE_ITP_NET_THREADS threads = 4
+ * waves; the grid is G = min(ceil(tiles / 4), MMPDE_ITP_NET_BLOCKS_PER_CU *
+ * compute units) workgroups; on its trip r = 0, 1, ... wave w of workgroup g
+ * takes tile (4 r + w) * G + g while that is below the tile count.  So some
+ * wave takes a second trip from 4 G + 1 tiles on.
+ * All three entries refuse with MMPDE_ERR_INVALID_ARG before any launch: a
+ * null net / shape, n_layers outside 1 .. MMPDE_ITP_MAX_LAYERS, widths[0] != 62,
+ * widths[n_layers] != 30, a hidden width outside 1 .. MMPDE_ITP_MAX_WIDTH
+ * (mmpde_itp_net_pack_bytes: returns 0); the pack also a null w[l] / b[l] of a
+ * used layer; pack and interp a null or not 16-byte aligned packed and
+ * packed_bytes below mmpde_itp_net_pack_bytes (the kernel never reads past an
+ * image built for another shape); interp also null src, vals, qry, idx or out,
+ * batches < 1, n_src < 30, n_qry < 1. */
+#define MMPDE_ITP_NET_THREADS 256
+#define MMPDE_ITP_NET_BLOCKS_PER_CU 4
+int mmpde_itp_interp_net(const float *src, const float *vals, const float *qry, const int32_t *idx,
+                         int64_t batches, int64_t n_src, int64_t n_qry, const mmpde_itp_net *shape,
+                         const void *packed, int64_t packed_bytes, const float *addend,
+                         const float *addend2, float *out, mmpde_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * DMM training (reference mesh/dmm_utils.py)
  * ---------------------------------------------------------------------- */

@@ -108,6 +108,15 @@ class ItpMlp(ctypes.Structure):
     _fields_ = [(n, _P) for n in ("w0", "b0", "w1", "b1", "w2", "b2")]
 
 
+ITP_MAX_LAYERS, ITP_MAX_WIDTH = 5, 256   # MMPDE_ITP_MAX_LAYERS / MMPDE_ITP_MAX_WIDTH
+
+
+class ItpNetShape(ctypes.Structure):
+    """mmpde_itp_net: n_layers Linears 62 -> hidden ... -> 30, torch [out, in] weights."""
+    _fields_ = [("n_layers", _I), ("widths", _I * (ITP_MAX_LAYERS + 1)), ("w", _P * ITP_MAX_LAYERS),
+                ("b", _P * ITP_MAX_LAYERS)]
+
+
 class RgemmArgs(ctypes.Structure):
     """mmpde_rgemm_args (include/mmpde_hip.h)."""
     _fields_ = [("m", _I64), ("kh", _I), ("layout", _I), ("w", _P * 2), ("ldw", _I64),
@@ -220,6 +229,9 @@ _SIGS = {
     "mmpde_itp_pack": (_I, [_P, _P, _P]),
     "mmpde_itp_interp": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P]),
     "mmpde_itp_interp_ex": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
+    "mmpde_itp_net_pack_bytes": (_I64, [_P]),
+    "mmpde_itp_net_pack": (_I, [_P, _P, _I64, _P]),
+    "mmpde_itp_interp_net": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _I64, _P, _P, _P, _P]),
     "mmpde_softmax_interp": (_I, [_P, _I64, _I64, _P, _I64, _P, _I64, _F, _P, _P]),
     "mmpde_softmax_interp_grad": (_I, [_P, _I64, _I64, _P, _I64, _P, _I64, _F, _P, _P, _P]),
     "mmpde_mesh_monitor_array": (_I, [_P, _I64, _I, _P, _P, _P, _P]),
@@ -248,7 +260,7 @@ def lib():
             try:
                 f = getattr(h, name)
             except AttributeError:
-                # an entry added without a version step (mmpde_dmm_mesh_relax, mmpde_mesh_quality in 12302)
+                # an entry added without a version step (mmpde_dmm_mesh_relax, mmpde_mesh_quality, mmpde_itp_*_net in 12302)
                 raise HipExtensionMissing(
                     f"{LIB_PATH} (ABI {h.mmpde_version()}) does not export {name}: it was built "
                     f"from an older tree; rebuild it with __graft_entry__.build()") from None

@@ -4,8 +4,11 @@ Parameters and state_dict keys match the reference: ``layers`` (mode '1'),
 ``layers2`` (mode '2'), the never-used ``layers3`` (kept for key parity) and the
 ``down`` residual-cut network (Linear MLP for the cylinder mesh, Conv2d stack
 for Burgers).  Modes '1'/'2' run inside the fused kNN-30 + MLP + weighted-sum
-kernel driven by GraphCreator_FS_2D.interpolate; ``forward(..., 'res_cut')``
-runs the ``down`` network on the skinny-GEMM / conv kernels.
+kernel driven by GraphCreator_FS_2D.interpolate (the reference's default widths
+128,64 on a kernel specialised to them, any other ``layers1`` / ``layers2`` of up
+to four hidden layers of width 1 to 256 on the shape-generic one, per mode);
+``forward(..., 'res_cut')`` runs the ``down`` network on the skinny-GEMM / conv
+kernels.
 
 In ``train()`` mode (mmpde.py:86, the ItpNet parameters are in the AdamW groups
 of mmpde.py:269-271) the forward follows interpolate.py:77-99 with device torch
@@ -112,27 +115,49 @@ class ItpNet(nn.Module):
         self._packs = {}
 
     # ----------------------------------------------------------------- packing
-    def packed(self, mode: str) -> torch.Tensor:
-        """Weights of mode '1' / '2' re-laid as the MFMA operand image of
-        mmpde_itp_interp (cached until a parameter changes)."""
+    def packed(self, mode: str, generic: bool = False):
+        """Weights of mode '1' / '2' re-laid as an MFMA operand image (cached
+        until a parameter changes), for ops.itp_interp.  The default widths
+        [62, 128, 64, 30] give the bare image tensor of mmpde_itp_interp; any
+        other shape within the limits of mmpde_itp_net (and the default ones
+        with ``generic``, for tests and timing) an ops.ItpNetPack for
+        mmpde_itp_interp_net."""
         mods = self.layers if mode == "1" else self.layers2
-        if [m.out_features for m in mods] != [128, 64, 30] or mods[0].in_features != 62:
-            raise NotImplementedError("fused ItpNet kernel needs layers [62, 128, 64, 30] "
-                                      "(the reference defaults --itpnet_node1/2 = 128,64)")
+        widths = [mods[0].in_features] + [m.out_features for m in mods]
+        generic = generic or widths != [62, 128, 64, 30]
+        if generic and (len(mods) > L.ITP_MAX_LAYERS or widths[0] != 62 or widths[-1] != 30
+                        or not all(1 <= w <= L.ITP_MAX_WIDTH for w in widths)):
+            raise NotImplementedError(
+                f"fused ItpNet kernel: layers {widths} are outside its limits, [62] + at most "
+                f"{L.ITP_MAX_LAYERS - 1} hidden layers of width 1 to {L.ITP_MAX_WIDTH} + [30]")
         ts = [t for m in mods for t in (m.weight, m.bias)]
         key = tuple((t.data_ptr(), t._version) for t in ts)
-        hit = self._packs.get(mode)
+        slot = (mode, generic)
+        hit = self._packs.get(slot)
         if hit is not None and hit[0] == key:
             return hit[1]
         L.require_device(*ts)
         f = [L.f32c(t) for t in ts]
-        mlp = L.ItpMlp(*[t.data_ptr() for t in f])
-        buf = torch.empty((L.lib().mmpde_itp_pack_bytes() // 4,), dtype=torch.float32,
-                          device=f[0].device)
-        L.check(L.lib().mmpde_itp_pack(ctypes.byref(mlp), L.ptr(buf), L.stream(buf.device)),
-                "mmpde_itp_pack")
-        self._packs[mode] = (key, buf, f)
-        return buf
+        lib = L.lib()
+        if generic:
+            net = L.ItpNetShape(n_layers=len(mods))
+            for i, w in enumerate(widths):
+                net.widths[i] = w
+            shape = L.ItpNetShape.from_buffer_copy(net)   # n_layers and widths only: no pointer
+            for i in range(len(mods)):
+                net.w[i], net.b[i] = f[2 * i].data_ptr(), f[2 * i + 1].data_ptr()
+            nbytes = lib.mmpde_itp_net_pack_bytes(ctypes.byref(net))
+            buf = torch.empty((nbytes // 4,), dtype=torch.float32, device=f[0].device)
+            L.check(lib.mmpde_itp_net_pack(ctypes.byref(net), L.ptr(buf), nbytes, L.stream(buf.device)),
+                    "mmpde_itp_net_pack")
+            pack = ops.ItpNetPack(buf, shape, nbytes)
+        else:
+            mlp = L.ItpMlp(*[t.data_ptr() for t in f])
+            pack = torch.empty((lib.mmpde_itp_pack_bytes() // 4,), dtype=torch.float32, device=f[0].device)
+            L.check(lib.mmpde_itp_pack(ctypes.byref(mlp), L.ptr(pack), L.stream(pack.device)),
+                    "mmpde_itp_pack")
+        self._packs[slot] = (key, pack, f)
+        return pack
 
     def weights(self, neighbors: torch.Tensor, query_points: torch.Tensor, mode: str):
         """interpolate.py:79-93: the 30 weights of every query from its neighbours'

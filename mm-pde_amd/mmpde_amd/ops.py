@@ -822,10 +822,29 @@ class Conv2dSame(torch.autograd.Function):
         return gx, gw, gb, None
 
 
-def itp_interp(src, vals, qry, idx, batches: int, packed: torch.Tensor, addend=None, addend2=None):
+class ItpNetPack:
+    """ItpNet.packed() of a shape the specialised kernel does not serve: the
+    image of mmpde_itp_net_pack, its size and the shape block (n_layers and
+    widths, no pointers) that mmpde_itp_interp_net reads at the call."""
+    __slots__ = ("image", "shape", "nbytes")
+
+    def __init__(self, image: torch.Tensor, shape, nbytes: int):
+        self.image, self.shape, self.nbytes = image, shape, nbytes
+
+    @property
+    def widths(self):
+        return list(self.shape.widths[:self.shape.n_layers + 1])
+
+
+def itp_interp(src, vals, qry, idx, batches: int, packed, addend=None, addend2=None):
     """ItpNet weights + weighted neighbour sum (interpolate.py:77-93,
     data_creator_2d.py:80-83), + addend, then + addend2 (both optional).
+    packed is ItpNet.packed(mode): the bare image of the default widths
+    (mmpde_itp_interp_ex) or an ItpNetPack (mmpde_itp_interp_net).
     Returns [batches * n_qry] fp32."""
+    net = packed if isinstance(packed, ItpNetPack) else None
+    if net is not None:
+        packed = net.image
     L.require_device(src, vals, qry, idx, packed)
     src = L.f32c(src).reshape(-1, 2)
     qry = L.f32c(qry).reshape(-1, 2)
@@ -834,6 +853,12 @@ def itp_interp(src, vals, qry, idx, batches: int, packed: torch.Tensor, addend=N
     out = torch.empty((batches * nq,), dtype=torch.float32, device=src.device)
     add = L.f32c(addend).reshape(-1) if addend is not None else None
     add2 = L.f32c(addend2).reshape(-1) if addend2 is not None else None
+    if net is not None:
+        L.check(L.lib().mmpde_itp_interp_net(L.ptr(src), L.ptr(vals), L.ptr(qry), L.ptr(idx.contiguous()),
+                                             batches, ns, nq, ctypes.byref(net.shape), L.ptr(packed),
+                                             net.nbytes, L.ptr(add), L.ptr(add2), L.ptr(out),
+                                             L.stream(src.device)), "mmpde_itp_interp_net")
+        return out
     L.check(L.lib().mmpde_itp_interp_ex(L.ptr(src), L.ptr(vals), L.ptr(qry), L.ptr(idx.contiguous()),
                                         batches, ns, nq, L.ptr(packed), L.ptr(add), L.ptr(add2),
                                         L.ptr(out), L.stream(src.device)), "mmpde_itp_interp_ex")
