@@ -996,6 +996,91 @@ int mmpde_softmax_interp_grad(const float *pts, int64_t n_pts, int64_t pts_sets,
                               const float *grad_out, float *grad_qry, mmpde_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * DMM training, the random-feature phase (reference mesh/dmm_utils.py:785-1076,
+ * random_feature_torch2 :351-388): out_nn's last Linear refitted by BFGS with
+ * every other weight frozen, phi = w . s + b.
+ * Added without a version step: a library reporting 12302 may or may not export
+ * these symbols; look them up before calling.
+ * ---------------------------------------------------------------------- */
+
+/* The sibling of mmpde_dmm_phi: the features s = second_out [n_grid, L'] and
+ * their derivatives in the grid row, per feature.  With a = T0 xi + t0_b,
+ * h = tanh a, P = W_o0[:, L:] T1 [L', th], c_b = W_o0[:, :L] branch_b +
+ * W_o0[:, L:] t1_b + b_o0:
+ *     z = P h + c_b,  s = tanh z
+ *     z_d = P (h' * T0[:, d]),  z_de = P (h'' * T0[:, d] * T0[:, e]),
+ *         h' = 1 - h^2, h'' = -2 h h'
+ *     s_d = (1 - s^2) z_d,  s_de = (1 - s^2) z_de - 2 s (1 - s^2) z_d z_e
+ * (z_d, z_de are the J and K tables of mmpde_dmm_mesh_*_hess).  The reference
+ * obtains them with 6 L' autograd.grad calls per batch (dmm_utils.py:883-905),
+ * s_xy and s_yx separately; they are equal, and one table s_xy serves for both.
+ * branch [B, L], grid [n_grid, 2] (row i belongs to trajectory i / (n_grid / B)),
+ * hd as for mmpde_dmm_phi (th <= 64).  Every pointer of mmpde_dmm_rf_out is
+ * nullable: a null table is not written, and with s_xx, s_xy, s_yy all null the
+ * second-order work is skipped (the first-order tables keep their bits).  s is,
+ * bit for bit, mmpde_dmm_phi's second_out (the same launches write it).
+ * workspace >= mmpde_dmm_rf_features_workspace_bytes(B, n_grid, L, L', th), 16-B
+ * aligned.  Stream-ordered, no allocation, no synchronisation: capturable.
+ * Refused before any launch: null branch / grid / hd / workspace / out, a
+ * misaligned workspace (16 B), grid (8 B) or table (4 B), batches < 1, n_grid < 1,
+ * n_grid % batches != 0; a head mmpde_dmm_phi does not take:
+ * MMPDE_ERR_UNSUPPORTED. */
+typedef struct {
+    float *s, *s_x, *s_y, *s_xx, *s_xy, *s_yy; /* [n_grid, L'] each */
+} mmpde_dmm_rf_out;
+int64_t mmpde_dmm_rf_features_workspace_bytes(int64_t batches, int64_t n_grid, int latent, int hidden,
+                                              int th);
+int mmpde_dmm_rf_features(const float *branch, int64_t batches, const float *grid, int64_t n_grid,
+                          const mmpde_dmm_head *hd, void *workspace, const mmpde_dmm_rf_out *out,
+                          mmpde_stream_t stream);
+
+/* random_feature_torch2 and its gradient in w [L']:
+ *     f = convex_rel (sum w^2)^2 + w1 loss_bound + w0 loss_in + w2 loss_convex
+ * with p = F w for each table F below (phi's derivatives at the sampled rows):
+ *     loss_bound  = mean over the four sides of mean(p_side^2)
+ *     (ux, uy)    = the softmax smoother (mmpde_softmax_interp, unit lattice,
+ *                   scale n) of field i / (m / bu) at (x1 + p_x, x2 + p_y)
+ *     a = ux (1 + p_xx) + uy p_xy,  c = ux p_xy + uy (1 + p_yy)
+ *     m_xi = 1 + sqrt(a^2 + c^2) / (0.01 alpha),  LHS = m_xi ((1 + p_xx)(1 + p_yy) - p_xy^2)
+ *     loss_in     = mean((LHS / RHS - 1)^2)
+ *     loss_convex = mean(min(0, 1 + p_xx)^2 + min(0, 1 + p_yy)^2)
+ * p_x and p_y reach f only through the smoother's query, so their gradient is the
+ * smoother's position VJP (mmpde_softmax_interp_grad).  Where a = c = 0 the
+ * square root has no derivative (autograd gives NaN there); that point
+ * contributes 0 to g.  so_xy stands for the reference's so_xy and so_yx.
+ * Outputs: f (one float), g [L'] = df/dw, parts [3] = (loss_in, loss_bound,
+ * loss_convex), lhs [m] (nullable).  Every reduction runs in a fixed order, no
+ * atomics: two calls on the same inputs give the same bits.  workspace >=
+ * mmpde_rf_objective_workspace_bytes(m, mb), 16-B aligned.  Stream-ordered and
+ * capturable.  Refused before any launch: a null pointer (lhs excepted), m < 1,
+ * mb < 1, hidden < 1, bu < 1, n < 2, m % bu != 0, misaligned pointers. */
+typedef struct {
+    const float *so_x, *so_y, *so_xx, *so_xy, *so_yy; /* interior tables [m, hidden] */
+    const float *b_x0, *b_x1, *b_y0, *b_y1; /* so_x on x = 0, x = 1, so_y on y = 0, y = 1: [mb, hidden] */
+    const float *x;                         /* [m, 2] sampled points */
+    const float *ux, *uy;                   /* [bu, n, n] monitor derivative fields */
+    const float *alpha, *rhs;               /* [bu] */
+    const float *lattice;                   /* [n*n, 2] the unit lattice, flat 'xy' order */
+    int64_t m, mb;
+    int hidden, bu, n;
+    float w0, w1, w2, convex_rel;
+} mmpde_rf_problem;
+int64_t mmpde_rf_objective_workspace_bytes(int64_t m, int64_t mb);
+int mmpde_rf_objective(const float *w, const mmpde_rf_problem *pb, void *workspace, float *f, float *g,
+                       float *parts, float *lhs, mmpde_stream_t stream);
+
+/* The two O(n^2) steps of BFGS on the inverse Hessian H [n, n] (row-major,
+ * symmetric), 1 <= n <= MMPDE_BFGS_MAX_N, sums in a fixed order:
+ * d_out = scale * H g, and the update (Nocedal & Wright (6.17))
+ *     H <- (I - rho s y^T) H (I - rho y s^T) + rho s s^T,  rho = 1 / y.s
+ * in place, skipped when y.s <= 1e-10; H stays symmetric bit for bit.
+ * workspace >= mmpde_bfgs_update_workspace_bytes(n), 16-B aligned. */
+#define MMPDE_BFGS_MAX_N 1024
+int mmpde_sym_matvec(const float *H, const float *g, int n, float *d_out, float scale, mmpde_stream_t stream);
+int64_t mmpde_bfgs_update_workspace_bytes(int n);
+int mmpde_bfgs_update(float *H, const float *s, const float *y, int n, void *workspace, mmpde_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Mesh quality of a moved mesh (reference mesh/dmm_utils.py:1162-1284,
  * evaluate_tri / evaluate), batched and per trajectory
  * ---------------------------------------------------------------------- */

@@ -226,4 +226,25 @@ __attribute__((visibility("hidden"))) int conv2d(const float *x, int64_t batches
                                                  const float *residual, int act, float *y,
                                                  hipStream_t st, unsigned *zero, int n_zero,
                                                  int circular = 0, int res_after_act = 0);
+
+// mmpde_dmm_phi (dmm.hip) in its two halves, for mmpde_dmm_rf_features
+// (dmm_rf.hip): the tables of the head on grid rows -- P [B, L'], Q [n_grid, L'],
+// J = dQ/dxi [n_grid, L'] float2 in ws (dmm_phi_floats floats, 16-B aligned) and,
+// with kout, K = dJ/dxi [n_grid, L', 3] -- and the row kernel that writes phi
+// (nullable) and second_out = tanh(P[b] + Q[i]) (nullable) from them.
+struct DmmPhiTables {
+    const float *p, *q;
+    const float2 *jac;
+    const float *k;
+};
+__attribute__((visibility("hidden"))) bool dmm_head_ok(const mmpde_dmm_head *hd);
+__attribute__((visibility("hidden"))) int64_t dmm_phi_floats(int64_t batches, int64_t n_grid, int latent,
+                                                             int hidden, int th);
+__attribute__((visibility("hidden"))) int dmm_phi_tables(const float *branch, int64_t batches,
+                                                         const float *grid, int64_t n_grid,
+                                                         const mmpde_dmm_head *hd, float *ws, float *kout,
+                                                         DmmPhiTables *t, hipStream_t st);
+__attribute__((visibility("hidden"))) int dmm_phi_rows(const DmmPhiTables &t, const mmpde_dmm_head *hd,
+                                                       const float *o1_b, int64_t n_grid, int64_t per,
+                                                       float *phi_out, float *second_out, hipStream_t st);
 }  // namespace mmpde_detail

@@ -655,7 +655,7 @@ __global__ __launch_bounds__(256) void det_reduce_kernel(const float *__restrict
 
 // phi[i] = w_o . tanh(P[b] + Q[i]) + b_o2, b = i / per (out_nn = DenseNet[2L, L', 1]
 // on cat(branch_b, trunk(grid_i)), dmm_model.py:190,213); second[i] = the tanh
-// row (rf=True's second_out).  One wave per grid row.
+// row (rf=True's second_out).  One wave per grid row.  phi and second nullable.
 __global__ __launch_bounds__(256) void phi_kernel(const float *__restrict__ P, const float *__restrict__ Q,
                                                   const float *__restrict__ wo, const float *__restrict__ bo,
                                                   int64_t n_grid, int64_t per, int hidden,
@@ -672,7 +672,7 @@ __global__ __launch_bounds__(256) void phi_kernel(const float *__restrict__ P, c
         acc += wo[kk] * t;
     }
     acc = wave_sum_full(acc);
-    if (lane == 0) phi[i] = acc + (bo ? bo[0] : 0.0f);
+    if (lane == 0 && phi) phi[i] = acc + (bo ? bo[0] : 0.0f);
 }
 
 struct HeadWs {
@@ -1295,16 +1295,53 @@ extern "C" int mmpde_dmm_phi(const float *branch, int64_t batches, const float *
     MMPDE_REQUIRE(n_grid % batches == 0 && al16(workspace) && ((uintptr_t)grid & 7u) == 0);
     if (!head_ok(hd)) return MMPDE_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
+    mmpde_detail::DmmPhiTables t;
+    const int rc = mmpde_detail::dmm_phi_tables(branch, batches, grid, n_grid, hd, (float *)workspace, nullptr,
+                                                &t, st);
+    if (rc) return rc;
+    return mmpde_detail::dmm_phi_rows(t, hd, o1_b, n_grid, n_grid / batches, phi_out, second_out, st);
+}
+
+// The two halves of mmpde_dmm_phi, shared with mmpde_dmm_rf_features (dmm_rf.hip),
+// whose s table is second_out written by the same launches.
+namespace mmpde_detail {
+
+bool dmm_head_ok(const mmpde_dmm_head *hd) { return head_ok(hd); }
+
+int64_t dmm_phi_floats(int64_t batches, int64_t n_grid, int latent, int hidden, int th) {
+    return head_floats(batches, n_grid, latent, hidden, th) + 64;
+}
+
+// trunk(grid), Q, J and P = Wb . branch + b_o1 in ws (dmm_phi_floats); kout
+// non-null: also K = dJ/dxi [n_grid, L', 3] (hess_k_kernel) into it
+int dmm_phi_tables(const float *branch, int64_t batches, const float *grid, int64_t n_grid,
+                   const mmpde_dmm_head *hd, float *ws, float *kout, DmmPhiTables *t, hipStream_t st) {
     const int L = hd->latent, Lp = hd->hidden;
-    HeadWs w = carve_head((float *)workspace, batches, n_grid, L, Lp, hd->th);
+    HeadWs w = carve_head(ws, batches, n_grid, L, Lp, hd->th);
     int rc = dmm_head_grid(grid, n_grid, hd, w, w.q, w.jac, st);  // trunk(grid), Q
     if (rc) return rc;
+    if (kout) {
+        hipLaunchKernelGGL(hess_k_kernel, dim3((unsigned)n_grid), dim3(256), 0, st, w.s, hd->th, w.gt, Lp,
+                           hd->t0_w, kout);
+        MMPDE_RET_LAUNCH();
+    }
     // P = Wb . branch + b_o1
     rc = mmpde_linear_skinny(branch, L, batches, L, hd->o0_w, 2 * L, hd->o0_b, Lp, MMPDE_ACT_NONE, w.p, Lp,
-                             stream);
+                             (mmpde_stream_t)st);
     if (rc) return rc;
-    hipLaunchKernelGGL(phi_kernel, dim3((unsigned)ceil_div(n_grid, 4)), dim3(256), 0, st, w.p, w.q, hd->o1_w,
-                       o1_b, n_grid, n_grid / batches, Lp, phi_out, second_out);
+    t->p = w.p;
+    t->q = w.q;
+    t->jac = w.jac;
+    t->k = kout;
+    return MMPDE_OK;
+}
+
+int dmm_phi_rows(const DmmPhiTables &t, const mmpde_dmm_head *hd, const float *o1_b, int64_t n_grid,
+                 int64_t per, float *phi_out, float *second_out, hipStream_t st) {
+    hipLaunchKernelGGL(phi_kernel, dim3((unsigned)ceil_div(n_grid, 4)), dim3(256), 0, st, t.p, t.q, hd->o1_w,
+                       o1_b, n_grid, per, hd->hidden, phi_out, second_out);
     MMPDE_RET_LAUNCH();
     return MMPDE_OK;
 }
+
+}  // namespace mmpde_detail

@@ -98,6 +98,22 @@ class DmmRelaxIO(ctypes.Structure):
                                   "guarded_total")]
 
 
+class DmmRfOut(ctypes.Structure):
+    """mmpde_dmm_rf_out: the feature tables of mmpde_dmm_rf_features, all nullable."""
+    _fields_ = [(n, _P) for n in ("s", "s_x", "s_y", "s_xx", "s_xy", "s_yy")]
+
+
+class RfProblem(ctypes.Structure):
+    """mmpde_rf_problem: the tables and sample of mmpde_rf_objective."""
+    _fields_ = [(n, _P) for n in ("so_x", "so_y", "so_xx", "so_xy", "so_yy", "b_x0", "b_x1", "b_y0", "b_y1",
+                                  "x", "ux", "uy", "alpha", "rhs", "lattice")] + \
+        [("m", _I64), ("mb", _I64), ("hidden", _I), ("bu", _I), ("n", _I), ("w0", _F), ("w1", _F), ("w2", _F),
+         ("convex_rel", _F)]
+
+
+BFGS_MAX_N = 1024   # MMPDE_BFGS_MAX_N
+
+
 class MeshQualityIO(ctypes.Structure):
     """mmpde_mesh_quality_io: the outputs of mmpde_mesh_quality, all nullable."""
     _fields_ = [(n, _P) for n in ("mean", "std", "range", "inverted", "area_ratio_min", "inverted_total",
@@ -225,6 +241,13 @@ _SIGS = {
     "mmpde_dmm_branch_array": (_I, [_P, _I64, _P, _P, _P, _P, _P]),
     "mmpde_dmm_phi_workspace_bytes": (_I64, [_I64, _I64, _I, _I, _I]),
     "mmpde_dmm_phi": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "mmpde_dmm_rf_features_workspace_bytes": (_I64, [_I64, _I64, _I, _I, _I]),
+    "mmpde_dmm_rf_features": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P]),
+    "mmpde_rf_objective_workspace_bytes": (_I64, [_I64, _I64]),
+    "mmpde_rf_objective": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "mmpde_sym_matvec": (_I, [_P, _P, _I, _P, _F, _P]),
+    "mmpde_bfgs_update_workspace_bytes": (_I64, [_I]),
+    "mmpde_bfgs_update": (_I, [_P, _P, _P, _I, _P, _P]),
     "mmpde_itp_pack_bytes": (_I64, []),
     "mmpde_itp_pack": (_I, [_P, _P, _P]),
     "mmpde_itp_interp": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P]),
@@ -260,7 +283,9 @@ def lib():
             try:
                 f = getattr(h, name)
             except AttributeError:
-                # an entry added without a version step (mmpde_dmm_mesh_relax, mmpde_mesh_quality, mmpde_itp_*_net in 12302)
+                # an entry added without a version step (mmpde_dmm_mesh_relax, mmpde_mesh_quality, mmpde_itp_*_net,
+                # the random-feature phase's mmpde_dmm_rf_features / mmpde_rf_objective / mmpde_sym_matvec /
+                # mmpde_bfgs_update in 12302)
                 raise HipExtensionMissing(
                     f"{LIB_PATH} (ABI {h.mmpde_version()}) does not export {name}: it was built "
                     f"from an older tree; rebuild it with __graft_entry__.build()") from None

@@ -207,8 +207,22 @@ class DMM(nn.Module):
         B = u.shape[0]
         if grid.shape[0] % B:
             raise ValueError("grid rows must be a multiple of the batch size")
+        branch = self._branch_train(u)
+        rep = grid.shape[0] // B
+        branch = branch[:, None, :].expand(B, rep, branch.shape[-1]).reshape(-1, branch.shape[-1])
+        trunk, _ = self.trunk(grid)
+        out, second = self.out_nn(torch.cat((branch, trunk.reshape(-1, branch.shape[-1])), dim=-1))
+        if not rf:
+            return out
+        return out, second, torch.ones_like(second).reshape(-1, 1)
+
+    def _branch_train(self, u):
+        """The branch of _forward_train [B, L] (dmm_model.py:188,197-210 in train()
+        mode): the graph branch's BatchNorms use batch statistics and advance
+        their running statistics once per call."""
+        B = u.shape[0]
         if self.mode == "array":
-            branch = self.branch(u.unsqueeze(1))
+            return self.branch(u.unsqueeze(1))
         else:
             og = torch.as_tensor(self.ori_grid).to(u.device, torch.float32).reshape(-1, 2)
             N = og.shape[0]
@@ -222,14 +236,7 @@ class DMM(nn.Module):
             for layer in self.gnn_layers:
                 h = layer(h, x, pos_x, pos_y, gnbr)
             h, _ = self.decoding_mlp(h)
-            branch = self.output_mlp(h.reshape(B, -1))
-        rep = grid.shape[0] // B
-        branch = branch[:, None, :].expand(B, rep, branch.shape[-1]).reshape(-1, branch.shape[-1])
-        trunk, _ = self.trunk(grid)
-        out, second = self.out_nn(torch.cat((branch, trunk.reshape(-1, branch.shape[-1])), dim=-1))
-        if not rf:
-            return out
-        return out, second, torch.ones_like(second).reshape(-1, 1)
+            return self.output_mlp(h.reshape(B, -1))
 
     # ----------------------------------------------------------------- packing
     def _check(self):
@@ -297,6 +304,43 @@ class DMM(nn.Module):
         self._pack = ((bp, hd), fh + fb)
         self._pack_key = key
         return self._pack[0]
+
+    def _head_params(self):
+        """The head alone as a _lib.DmmHead (with the float32 tensors it points
+        to), in either mode: the head has no BatchNorm, so it is the same
+        function in train() and eval()."""
+        tl, ol = self.trunk.layers, self.out_nn.layers
+        if len(tl) != 2 or len(ol) != 2 or ol[1].out_features != 1:
+            raise NotImplementedError("trunk DenseNet[2, th, L] / out_nn DenseNet[2L, L', 1] only")
+        fh = [L.f32c(t) for t in self._tensors()[0]]
+        hd = L.DmmHead(fh[0].data_ptr(), fh[1].data_ptr(), fh[2].data_ptr(), fh[3].data_ptr(),
+                       tl[0].out_features, tl[1].out_features, fh[4].data_ptr(),
+                       fh[5].data_ptr(), fh[6].data_ptr(), ol[0].out_features)
+        return hd, fh
+
+    def rf_features(self, u: torch.Tensor, grid: torch.Tensor, second_order: bool = True,
+                    branch: torch.Tensor | None = None):
+        """The random features of forward(u, grid, rf=True) -- second_out, the tanh
+        layer under out_nn's last Linear -- and their derivatives in grid, per
+        feature (ops.dmm_rf_features): what the reference's random-feature phase
+        builds with 6 L' autograd.grad calls (mesh/dmm_utils.py:883-905).
+        u, grid as for forward; branch: the branch output [B, L] to use instead
+        of computing it from u.  In eval() the branch is branch_features(u); in
+        train() it comes from the torch ops of the train()-mode forward, so the
+        graph branch's BatchNorms use batch statistics and advance their running
+        statistics once per call, as the reference's model(u, x_, rf=True) does.
+        Nothing is differentiable here.  Deliberate difference: one table s_xy
+        for the reference's so_xy and so_yx (they are equal).
+        Returns ops.RfFeatures(s, s_x, s_y, s_xx, s_xy, s_yy), [rows, L'] each,
+        the last three None with second_order=False."""
+        L.require_device(u, grid)
+        with torch.no_grad():
+            if branch is None:
+                branch = self._branch_train(u) if self.training else self.branch_features(u)
+            hd, keep = self._head_params()
+            out = ops.dmm_rf_features(branch, grid, hd, second_order)
+        del keep
+        return out
 
     def grid_nbr(self, grid: torch.Tensor, k: int = 35) -> torch.Tensor:
         """kNN-35 table of the fixed grid (reference dmm_model.py:222-234 builds it

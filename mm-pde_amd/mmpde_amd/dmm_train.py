@@ -1,9 +1,25 @@
 """DMM training: the Monge-Ampere mesh-mover fit of the reference
 (mesh/dmm_utils.py:29-267 sampling / monitor / interpolation, :391-1095
-train_MA_res's Adam and LBFGS phases, :1149-1284 evaluate_tri / evaluate),
-SURVEY.md §8(f) row 4.  The random-feature branch (torchmin BFGS,
-dmm_utils.py:290-388 and the rf path of mesh/dmm.py) needs pytorch-minimize,
-which is not available, and is not built.
+train_MA_res's Adam, LBFGS and random-feature phases, :1149-1284 evaluate_tri /
+evaluate), SURVEY.md §8(f) row 4.
+
+The random-feature phase (args.rf, the reference's default: dmm_utils.py:785-1076
+with random_feature_torch2, :351-388) refits out_nn's last Linear with every
+other weight frozen: the tanh layer under it is a fixed feature map s, phi =
+w . s + b, and w is fitted to the Monge-Ampere loss by BFGS with a strong-Wolfe
+line search.  Here the features' derivatives come from one kernel
+(DMM.rf_features, mmpde_dmm_rf_features) instead of 6 L' autograd.grad calls per
+batch, the objective and its gradient from mmpde_rf_objective, and the
+optimiser is mmpde_amd.minimize.minimize_bfgs.  Three stated differences:
+* the reference computes so_xy and so_yx separately; they are equal, and one
+  table serves for both;
+* where the monitor's square root has no derivative (u_xi_x = u_xi_y = 0)
+  autograd gives NaN; that point contributes 0 to the gradient here;
+* the reference's optimiser is pytorch-minimize's bfgs (line_search=
+  'strong-wolfe'), which is not a dependency and could not be run for
+  comparison.  minimize_bfgs is written from the textbook algorithm and calls
+  the same torch line-search routine that package appears to use; no further
+  parity is claimed.  rf_opt_alg='Newton' (Newton-CG) is not built.
 
 What runs where:
 * the DMM forward in train() mode: differentiable device torch ops
@@ -20,10 +36,12 @@ What runs where:
 
 ``train_MA_res`` keeps the reference's signature, optimisers (Adam with weight
 decay + MultiStepLR [100, 150]; LBFGS with tolerances -1 + MultiStepLR
-[75, 125]), loss weights, logging lists and checkpoint dict.
+[75, 125]; BFGS on the last layer), loss weights, logging lists and checkpoint
+dict.
 """
 from __future__ import annotations
 
+import collections
 import os
 from datetime import datetime
 
@@ -316,10 +334,63 @@ def objective(model, args, sample, nx, init_mesh, device):
     return loss, loss_in, loss_bound, loss_convex, lhs, rhs
 
 
+# --------------------------------------------------------------------------- random features
+RfEpoch = collections.namedtuple("RfEpoch", ("sample", "f_before", "f_after", "nit", "nfev", "status"))
+RfEpoch.__doc__ = """random_feature_epoch's record: the epoch's sample (as _sample returns it), the
+objective at the weight it started from and at the weight it wrote, and minimize_bfgs's nit,
+nfev and status."""
+
+
+def _rf_check_args(args):
+    alg = getattr(args, "rf_opt_alg", "BFGS")
+    if alg == "Newton":
+        raise NotImplementedError("rf_opt_alg='Newton' (pytorch-minimize's newton-cg) is not built: only "
+                                  "'BFGS' (mmpde_amd.minimize.minimize_bfgs) is")
+    if alg != "BFGS":
+        raise ValueError(f"rf_opt_alg {alg!r}: 'BFGS'")
+    if int(args.batch_size_x_rf / 4) == 0:
+        raise ValueError("batch_size_x_rf must be at least 4: each side takes batch_size_x_rf // 4 boundary "
+                         "points (Mb == 0), and the reference's MSE over an empty side is NaN")
+
+
+def random_feature_epoch(model, args, all_u, device, dense=None):
+    """One epoch of the random-feature phase (dmm_utils.py:787-945): draw a
+    sample (batch_size_x_rf points of batch_size_u_rf fields, interior then
+    boundary, the numpy draws in the reference's order), take the features'
+    derivatives at the four sides (their own fields, first order) and at the
+    interior points (second order) -- five model calls, in the reference's
+    order -- and fit out_nn.layers[-1].weight to random_feature_torch2 by BFGS
+    from its current value (args.max_iter iterations, args.convex_rel, the loss
+    weights).  Only that weight is written; in train() mode the graph branch's
+    BatchNorm statistics advance once per model call, as in the reference.
+    dense: minimize_bfgs's backend (None: the HIP one).  Returns an RfEpoch."""
+    from . import ops
+    from .minimize import minimize_bfgs
+
+    _rf_check_args(args)
+    bx, bu = args.batch_size_x_rf, args.batch_size_u_rf
+    sample = _sample(args, all_u, bx, bu, device)
+    u, ux, uy, alpha, rhs, x, bounds, bound_us = sample
+    sides = []
+    for side, (b, b_u) in enumerate(zip(bounds, bound_us)):
+        ft = model.rf_features(b_u, b, second_order=False)
+        sides.append(ft.s_x if side < 2 else ft.s_y)
+    interior = model.rf_features(u, x, second_order=True)
+    obj = ops.RfObjective(interior, sides, x, ux, uy, alpha, rhs, args.loss_weight0, args.loss_weight1,
+                          args.loss_weight2, args.convex_rel)
+    weight = model.out_nn.layers[-1].weight
+    w0 = weight.detach().reshape(-1).float().clone()
+    res = minimize_bfgs(obj, w0, int(args.max_iter), dense)
+    f_before = float(obj(w0)[0])
+    with torch.no_grad():
+        weight.copy_(res.x.reshape(weight.shape))
+    return RfEpoch(sample, f_before, float(res.fun), res.nit, res.nfev, res.status)
+
+
 # --------------------------------------------------------------------------- training
 def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_epoch_lbfgs, device,
                  save_dir=None, evaluate_every=1, reference_save_path=False):  # noqa: N802 - reference name
-    """dmm_utils.py:391-1095 without the random-feature branch: n_epoch_adam
+    """dmm_utils.py:391-1095: n_epoch_adam
     epochs of Adam then n_epoch_lbfgs of LBFGS, each epoch max(1, train_sample_grid
     T / (bx bu)) draws of fresh samples; per epoch the equation residual of the
     last logged draw, the scheduler step, evaluate[_tri] on the train and test
@@ -327,8 +398,18 @@ def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_e
     args.experiment, as the reference; False: not saved).  Returns the
     reference's 15-tuple (dmm_utils.py:1094-1095): model, loss_in, loss_bound,
     loss_convex, test_equ_loss / max / min / mid, train_std, train_minmax,
-    test_std, test_minmax, itp_list1, itp_list2 (empty: filled only by the
-    random-feature branch), logs_txt.
+    test_std, test_minmax, itp_list1, itp_list2 (empty: the reference creates
+    them, dmm_utils.py:412-413, and never appends to them), logs_txt.
+
+    With args.rf true (absent: false) args.epochs_rf epochs of the
+    random-feature phase follow (dmm_utils.py:785-1076), epoch numbers
+    continuing: random_feature_epoch, then the reference's check pass (:950-1061)
+    -- a fresh sample of the rf batch sizes through objective(), loss_in,
+    loss_bound and the equation residual appended every epoch (the reference
+    appends test_equ_loss alone; max, min and median are appended too here, so
+    that the four lists stay the same length) -- the log lines, evaluate[_tri]
+    and the checkpoint as in the other phases.  rf_opt_alg='Newton' raises
+    NotImplementedError before any epoch runs.
 
     Checkpoint file: 'dmm_{experiment}_epoch{N}.pt' in save_dir, one per epoch;
     reference_save_path=True writes the reference's name instead,
@@ -364,43 +445,17 @@ def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_e
             log["RHS"].append(rhs)
         counters[phase] += 1
 
-    for epoch in range(1, n_epoch_adam + n_epoch_lbfgs + 1):
-        start = datetime.now()
-        adam = epoch < n_epoch_adam + 1
-        bx = args.batch_size_x_adam if adam else args.batch_size_x_lbfgs
-        bu = args.batch_size_u_adam if adam else args.batch_size_u_lbfgs
-        draws = max(1, int(args.train_sample_grid * all_u.shape[0] / (bx * bu)))
-        for _ in range(draws):
-            if adam:
-                sample = _sample(args, all_u, bx, bu, device)
-                opt_adam.zero_grad()
-                loss, li, lb, lc, lhs, rhs = objective(model, args, sample, bx, init_mesh, device)
-                loss.backward()
-                record(0, li, lb, lc, lhs, rhs)
-                opt_adam.step()
-            else:
-                def closure():
-                    sample = _sample(args, all_u, bx, bu, device)
-                    opt_lbfgs.zero_grad()
-                    loss, li, lb, lc, lhs, rhs = objective(model, args, sample, bx, init_mesh, device)
-                    loss.backward()
-                    record(1, li, lb, lc, lhs, rhs)
-                    return loss
-                opt_lbfgs.step(closure)
-        if log["LHS"] and log["LHS"][-1] is not None:
-            # as dmm_utils.py:689: LHS [P, 1] / RHS [nu] broadcasts to the [P, nu]
-            # table of every (point, field) pair (a reference quirk, kept)
-            equ = log["LHS"][-1] / log["RHS"][-1] - torch.tensor(1).to(device)
-            log["test_equ_loss"].append(torch.mean(torch.abs(equ)).item())
-            log["test_equ_max"].append(torch.max(equ).item())
-            log["test_equ_min"].append(torch.min(equ).item())
-            log["test_equ_mid"].append(torch.median(equ).item())
-        (sch_adam if adam else sch_lbfgs).step()
-        line = "Epoch: {} | Loss in: {} | Loss bound: {} | Loss convex: {}".format(
-            epoch, log["loss_in"][-1], log["loss_bound"][-1], log["loss_convex"][-1])
-        if log["test_equ_loss"]:
-            line += " | Test equ loss: {:1.4f}".format(log["test_equ_loss"][-1])
-        log["logs_txt"].append(f"{datetime.now() - start} " + line)
+    def equ_residual(lhs, rhs):
+        # as dmm_utils.py:689: LHS [P, 1] / RHS [nu] broadcasts to the [P, nu]
+        # table of every (point, field) pair (a reference quirk, kept)
+        equ = lhs / rhs - torch.tensor(1).to(device)
+        log["test_equ_loss"].append(torch.mean(torch.abs(equ)).item())
+        log["test_equ_max"].append(torch.max(equ).item())
+        log["test_equ_min"].append(torch.min(equ).item())
+        log["test_equ_mid"].append(torch.median(equ).item())
+
+    def finish_epoch(epoch):
+        """evaluate[_tri] when evaluate_every says so, and the checkpoint."""
         if evaluate_every and epoch % evaluate_every == 0:
             if args.experiment == "burgers":
                 tr = evaluate(model, all_u, device, epoch)
@@ -432,6 +487,60 @@ def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_e
             else:
                 name = f"dmm_{args.experiment}_epoch{epoch}.pt"
             torch.save(ckpt, os.path.join(d, name))
+
+    rf = bool(getattr(args, "rf", False))
+    if rf:
+        _rf_check_args(args)
+
+    for epoch in range(1, n_epoch_adam + n_epoch_lbfgs + 1):
+        start = datetime.now()
+        adam = epoch < n_epoch_adam + 1
+        bx = args.batch_size_x_adam if adam else args.batch_size_x_lbfgs
+        bu = args.batch_size_u_adam if adam else args.batch_size_u_lbfgs
+        draws = max(1, int(args.train_sample_grid * all_u.shape[0] / (bx * bu)))
+        for _ in range(draws):
+            if adam:
+                sample = _sample(args, all_u, bx, bu, device)
+                opt_adam.zero_grad()
+                loss, li, lb, lc, lhs, rhs = objective(model, args, sample, bx, init_mesh, device)
+                loss.backward()
+                record(0, li, lb, lc, lhs, rhs)
+                opt_adam.step()
+            else:
+                def closure():
+                    sample = _sample(args, all_u, bx, bu, device)
+                    opt_lbfgs.zero_grad()
+                    loss, li, lb, lc, lhs, rhs = objective(model, args, sample, bx, init_mesh, device)
+                    loss.backward()
+                    record(1, li, lb, lc, lhs, rhs)
+                    return loss
+                opt_lbfgs.step(closure)
+        if log["LHS"] and log["LHS"][-1] is not None:
+            equ_residual(log["LHS"][-1], log["RHS"][-1])
+        (sch_adam if adam else sch_lbfgs).step()
+        line = "Epoch: {} | Loss in: {} | Loss bound: {} | Loss convex: {}".format(
+            epoch, log["loss_in"][-1], log["loss_bound"][-1], log["loss_convex"][-1])
+        if log["test_equ_loss"]:
+            line += " | Test equ loss: {:1.4f}".format(log["test_equ_loss"][-1])
+        log["logs_txt"].append(f"{datetime.now() - start} " + line)
+        finish_epoch(epoch)
+
+    first_rf = n_epoch_adam + n_epoch_lbfgs + 1
+    for epoch in range(first_rf, first_rf + (args.epochs_rf if rf else 0)):
+        start = datetime.now()
+        rec = random_feature_epoch(model, args, all_u, device)
+        log["logs_txt"].append("{} random feature method epoch {}: f {} -> {} in {} iterations, {} evaluations"
+                               .format(datetime.now() - start, epoch, rec.f_before, rec.f_after, rec.nit, rec.nfev))
+        # the check pass (dmm_utils.py:950-1061): a fresh sample through the full model
+        bx = args.batch_size_x_rf
+        sample = _sample(args, all_u, bx, args.batch_size_u_rf, device)
+        _, li, lb, _, lhs, rhs = objective(model, args, sample, bx, False, device)
+        equ_residual(lhs.detach(), rhs)
+        log["loss_in"].append(li.item())
+        log["loss_bound"].append(lb.item())
+        log["logs_txt"].append("Epoch: {} | Loss in: {} | Loss bound: {} | Loss convex: {} | Test equ loss: {:1.4f}"
+                               .format(epoch, log["loss_in"][-1], log["loss_bound"][-1], 0, log["test_equ_loss"][-1]))
+        finish_epoch(epoch)
     return (model, log["loss_in"], log["loss_bound"], log["loss_convex"], log["test_equ_loss"],
             log["test_equ_max"], log["test_equ_min"], log["test_equ_mid"], log["train_std"],
             log["train_minmax"], log["test_std"], log["test_minmax"], [], [], log["logs_txt"])

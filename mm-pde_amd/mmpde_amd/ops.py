@@ -927,6 +927,154 @@ def mesh_relax(mesh: torch.Tensor, xi: torch.Tensor, hess: torch.Tensor | None =
     return mesh, alpha_b, lam, detmin, folds
 
 
+# --------------------------------------------------------------------------- random-feature phase
+RfFeatures = collections.namedtuple("RfFeatures", ("s", "s_x", "s_y", "s_xx", "s_xy", "s_yy"))
+RfFeatures.__doc__ = """ops.dmm_rf_features's tables, [n_grid, L'] each: the features s = DMM.forward(rf=True)'s
+second_out and their derivatives in the grid row; s_xx, s_xy, s_yy are None with second_order=False."""
+
+
+def dmm_rf_features(branch: torch.Tensor, grid: torch.Tensor, head_params, second_order: bool = True,
+                    workspace: torch.Tensor | None = None) -> RfFeatures:
+    """mmpde_dmm_rf_features: the random features of the DMM head and their
+    derivatives per feature, which the reference's random-feature phase takes
+    from 6 L' autograd.grad calls per batch (mesh/dmm_utils.py:883-905).
+    branch [B, L] (the model's branch output), grid [n_grid, 2] (row i belongs to
+    trajectory i // (n_grid // B)), head_params: the model's _lib.DmmHead.
+    Deliberate difference: the reference computes so_xy and so_yx separately;
+    they are equal, and the one table s_xy stands for both.  s is bit for bit
+    mmpde_dmm_phi's second_out; with second_order=False the first-order tables
+    keep their bits.  No synchronisation; capturable given a workspace."""
+    L.require_device(branch, grid)
+    branch = L.f32c(branch)
+    grid = L.f32c(grid).reshape(-1, 2)
+    hd = head_params
+    if branch.dim() != 2 or branch.shape[1] != hd.latent:
+        raise ValueError("branch must be [B, L]")
+    B, ng = branch.shape[0], grid.shape[0]
+    if B < 1 or ng < 1 or ng % B:
+        raise ValueError("grid rows must be a multiple of the batch size")
+    lib = L.lib()
+    nb = lib.mmpde_dmm_rf_features_workspace_bytes(B, ng, hd.latent, hd.hidden, hd.th)
+    if workspace is None:
+        workspace = torch.empty((nb // 4,), dtype=torch.float32, device=grid.device)
+    else:
+        L.require_device(workspace)
+        if workspace.numel() * workspace.element_size() < nb:
+            raise ValueError("workspace is smaller than mmpde_dmm_rf_features_workspace_bytes")
+    tabs = [torch.empty((ng, hd.hidden), dtype=torch.float32, device=grid.device)
+            for _ in range(6 if second_order else 3)] + [None] * (0 if second_order else 3)
+    out = L.DmmRfOut(*[L.ptr(t) for t in tabs])
+    L.check(lib.mmpde_dmm_rf_features(L.ptr(branch), B, L.ptr(grid), ng, ctypes.byref(hd), L.ptr(workspace),
+                                      ctypes.byref(out), L.stream(grid.device)), "mmpde_dmm_rf_features")
+    return RfFeatures(*tabs)
+
+
+class RfObjective:
+    """random_feature_torch2 (mesh/dmm_utils.py:351-388) and its gradient on
+    mmpde_rf_objective: f(w) = convex_rel (sum w^2)^2 + w1 loss_bound + w0 loss_in
+    + w2 loss_convex for the last Linear's weight w [L'] over fixed feature tables.
+    interior: RfFeatures of the sampled points x [M, 2] (second order); sides:
+    the four boundary tables (s_x on x = 0 and x = 1, s_y on y = 0 and y = 1,
+    [Mb, L'] each); ux, uy [bu, n, n], alpha, rhs [bu]: the sample's monitor
+    fields, points i bx .. i bx + bx - 1 reading field i.
+    ``obj(w)`` returns (f, g) as device tensors (f a 0-dim view); parts =
+    (loss_in, loss_bound, loss_convex) and lhs [M] are those of the last call.
+    Every call writes the same buffers: clone what must outlive the next call.
+    Deliberate differences: one s_xy table for the reference's so_xy and so_yx;
+    where the monitor's square root has no derivative (u_xi_x = u_xi_y = 0,
+    autograd: NaN) the point contributes 0 to g.  Two calls on the same inputs
+    give the same bits (fixed-order sums, no atomics)."""
+
+    def __init__(self, interior: RfFeatures, sides, x, ux, uy, alpha, rhs, w0, w1, w2, convex_rel):
+        from .dmm_train import unit_lattice
+
+        tabs = [interior.s_x, interior.s_y, interior.s_xx, interior.s_xy, interior.s_yy]
+        sides = list(sides)
+        if len(sides) != 4 or any(t.dim() != 2 for t in sides) or any(t.shape != sides[0].shape for t in sides):
+            raise ValueError("sides: four [Mb, L'] tables")
+        if sides[0].shape[0] == 0:
+            raise ValueError("no boundary points (Mb == 0): the reference's MSE over an empty side is NaN; "
+                             "batch_size_x_rf must be at least 4")
+        L.require_device(*tabs, *sides, x, ux, uy, alpha, rhs)
+        sides = [L.f32c(t) for t in sides]
+        tabs = [L.f32c(t) for t in tabs]
+        x = L.f32c(x).reshape(-1, 2)
+        M, n_feat = tabs[0].shape
+        ux, uy = L.f32c(ux), L.f32c(uy)
+        bu, n = ux.shape[0], ux.shape[-1]
+        alpha, rhs = L.f32c(alpha).reshape(-1), L.f32c(rhs).reshape(-1)
+        if any(t.shape != (M, n_feat) for t in tabs) or x.shape[0] != M or sides[0].shape[1] != n_feat:
+            raise ValueError("the interior tables must be [M, L'] for x [M, 2], the sides [Mb, L']")
+        if ux.shape != (bu, n, n) or uy.shape != ux.shape or alpha.numel() != bu or rhs.numel() != bu or M % bu:
+            raise ValueError("ux, uy [bu, n, n], alpha, rhs [bu], bu dividing M")
+        dev = x.device
+        lat = unit_lattice(n, dev)
+        self._keep = (tabs, sides, x, ux, uy, alpha, rhs, lat)
+        self.pb = L.RfProblem(*[L.ptr(t) for t in tabs], *[L.ptr(t) for t in sides], L.ptr(x), L.ptr(ux),
+                              L.ptr(uy), L.ptr(alpha), L.ptr(rhs), L.ptr(lat), M, sides[0].shape[0], n_feat, bu,
+                              n, float(w0), float(w1), float(w2), float(convex_rel))
+        self.n = n_feat
+        nb = L.lib().mmpde_rf_objective_workspace_bytes(M, sides[0].shape[0])
+        self.ws = torch.empty((nb // 4,), dtype=torch.float32, device=dev)
+        self.fbuf = torch.empty((4,), dtype=torch.float32, device=dev)   # f, parts[3]
+        self.g = torch.empty((n_feat,), dtype=torch.float32, device=dev)
+        self.lhs = torch.empty((M,), dtype=torch.float32, device=dev)
+
+    @property
+    def parts(self):
+        return self.fbuf[1:]
+
+    def __call__(self, w: torch.Tensor):
+        L.require_device(w)
+        w = L.f32c(w).reshape(-1)
+        if w.numel() != self.n:
+            raise ValueError(f"w must have {self.n} entries")
+        L.check(L.lib().mmpde_rf_objective(L.ptr(w), ctypes.byref(self.pb), L.ptr(self.ws), L.ptr(self.fbuf),
+                                           L.ptr(self.g), self.fbuf.data_ptr() + 4, L.ptr(self.lhs),
+                                           L.stream(w.device)), "mmpde_rf_objective")
+        return self.fbuf[0], self.g
+
+
+def _dense_check(H, n, *vecs):
+    if n < 1 or n > L.BFGS_MAX_N:
+        raise ValueError(f"n = {n}: the dense BFGS operations take 1 <= n <= {L.BFGS_MAX_N}")
+    L.require_device(H, *vecs)
+    if H.dtype != torch.float32 or not H.is_contiguous() or H.shape != (n, n):
+        raise ValueError("H must be a contiguous float32 [n, n] tensor")
+    for v in vecs:
+        if v.dtype != torch.float32 or not v.is_contiguous() or v.numel() != n:
+            raise ValueError("vectors must be contiguous float32 [n] tensors")
+
+
+def sym_matvec(H: torch.Tensor, g: torch.Tensor, scale: float = 1.0, out: torch.Tensor | None = None):
+    """out = scale * H g for H [n, n] float32, n <= 1024 (mmpde_sym_matvec): one wave
+    per row, sums in a fixed order."""
+    n = g.numel()
+    _dense_check(H, n, g)
+    if out is None:
+        out = torch.empty_like(g)
+    _dense_check(H, n, out)
+    L.check(L.lib().mmpde_sym_matvec(L.ptr(H), L.ptr(g), n, L.ptr(out), float(scale), L.stream(g.device)),
+            "mmpde_sym_matvec")
+    return out
+
+
+def bfgs_update(H: torch.Tensor, s: torch.Tensor, y: torch.Tensor, workspace: torch.Tensor | None = None):
+    """H <- (I - rho s y^T) H (I - rho y s^T) + rho s s^T in place, rho = 1 / y.s
+    (mmpde_bfgs_update), skipped on the device when y.s <= 1e-10; a symmetric H
+    stays symmetric bit for bit."""
+    n = s.numel()
+    _dense_check(H, n, s, y)
+    nb = L.lib().mmpde_bfgs_update_workspace_bytes(n)
+    if workspace is None:
+        workspace = torch.empty((nb // 4,), dtype=torch.float32, device=H.device)
+    elif workspace.numel() * workspace.element_size() < nb:
+        raise ValueError("workspace is smaller than mmpde_bfgs_update_workspace_bytes")
+    L.check(L.lib().mmpde_bfgs_update(L.ptr(H), L.ptr(s), L.ptr(y), n, L.ptr(workspace), L.stream(H.device)),
+            "mmpde_bfgs_update")
+    return H
+
+
 # --------------------------------------------------------------------------- mesh quality
 MESH_QUALITY_MAX_N = 256   # include/mmpde_hip.h MMPDE_MESH_QUALITY_MAX_N
 
