@@ -1034,6 +1034,61 @@ int mmpde_dmm_rf_features(const float *branch, int64_t batches, const float *gri
                           const mmpde_dmm_head *hd, void *workspace, const mmpde_dmm_rf_out *out,
                           mmpde_stream_t stream);
 
+/* The Monge-Ampere jet of the head, (phi, phi_x, phi_y, phi_xx, phi_xy, phi_yy)
+ * per grid row, and its first-order gradients: what the Adam and LBFGS phases
+ * of DMM training need of the head, without autograd through out_nn.  In the
+ * notation above, with v_0 = h, v_d = h' T0[:, d], v_de = h'' T0[:, d] T0[:, e],
+ * s' = 1 - s^2, s'' = -2 s s', and w_o = out_nn's last weight:
+ *     z = P v_0 + c_b,  z_d = P v_d,  z_de = P v_de,  s = tanh z
+ *     phi    = w_o . s + b_o1
+ *     phi_d  = w_o . (s' z_d)
+ *     phi_de = w_o . (s' z_de + s'' z_d z_e)
+ * i.e. mmpde_dmm_rf_features' tables contracted with w_o, but no [n_grid, L']
+ * table is ever held: a tile of 16 rows keeps its v_* [16, th] in LDS and z_* =
+ * P v_* comes from the exact-f32 MFMA tile by tile.  Every pointer of
+ * mmpde_dmm_jet_out is nullable; with phi_xx, phi_xy, phi_yy all null the
+ * second-order work is skipped and the others keep their bits.  o1_b nullable
+ * (0).
+ * mmpde_dmm_jet_grad: the gradient of sum_c <cot_c, jet_c> in branch and the
+ * seven head tensors (the grid rows are data).  A null cotangent is zero.  It
+ * recomputes z_* from v_* per tile (twice: once per row tile for dv_* = P^T
+ * dz_*, once per feature block for dP = sum dz_* (x) v_*) and needs the third
+ * derivatives of both tanh layers.  Every output is required and overwritten,
+ * not accumulated into: d_branch [B, L], d_t0_w [th, 2], d_t0_b [th], d_t1_w
+ * [L, th], d_t1_b [L], d_o0_w [L', 2L] (both halves), d_o0_b [L'], d_o1_w [L'],
+ * d_o1_b [1].  o1_b is not read.
+ * workspace >= mmpde_dmm_jet_workspace_bytes(B, n_grid, L, L', th) serves both
+ * calls, 16-B aligned: P, c_b and the backward's partial sums (128 partial dP
+ * [L', th], one row of L' floats per tile), far below one [n_grid, L'] table at
+ * training sizes.  A tile never spans two trajectories: B ceil(n_grid / B / 16)
+ * tiles.  Stream-ordered, no allocation, no synchronisation: capturable.  Every
+ * sum runs in a fixed order, no atomics: two calls on the same inputs give the
+ * same bits.
+ * Refused before any launch: null branch / grid / hd / workspace / out (cot,
+ * grads, any gradient pointer), a misaligned workspace (16 B), grid (8 B) or
+ * array (4 B), batches < 1, n_grid < 1, n_grid % batches != 0;
+ * a head mmpde_dmm_phi does not take: MMPDE_ERR_UNSUPPORTED
+ * (mmpde_dmm_jet_workspace_bytes: 0 for th > 64 or a non-positive size).
+ * Added without a version step, as the entries above. */
+typedef struct {
+    float *phi, *phi_x, *phi_y, *phi_xx, *phi_xy, *phi_yy; /* [n_grid] each */
+} mmpde_dmm_jet_out;
+typedef struct {
+    const float *phi, *phi_x, *phi_y, *phi_xx, *phi_xy, *phi_yy; /* [n_grid] each, null: zero */
+} mmpde_dmm_jet_cot;
+typedef struct {
+    float *d_branch;
+    float *d_t0_w, *d_t0_b, *d_t1_w, *d_t1_b, *d_o0_w, *d_o0_b, *d_o1_w, *d_o1_b;
+} mmpde_dmm_jet_grads;
+int64_t mmpde_dmm_jet_workspace_bytes(int64_t batches, int64_t n_grid, int latent, int hidden, int th);
+int mmpde_dmm_jet(const float *branch, int64_t batches, const float *grid, int64_t n_grid,
+                  const mmpde_dmm_head *hd, const float *o1_b, void *workspace,
+                  const mmpde_dmm_jet_out *out, mmpde_stream_t stream);
+int mmpde_dmm_jet_grad(const float *branch, int64_t batches, const float *grid, int64_t n_grid,
+                       const mmpde_dmm_head *hd, const float *o1_b, void *workspace,
+                       const mmpde_dmm_jet_cot *cot, const mmpde_dmm_jet_grads *grads,
+                       mmpde_stream_t stream);
+
 /* random_feature_torch2 and its gradient in w [L']:
  *     f = convex_rel (sum w^2)^2 + w1 loss_bound + w0 loss_in + w2 loss_convex
  * with p = F w for each table F below (phi's derivatives at the sampled rows):

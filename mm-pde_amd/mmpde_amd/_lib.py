@@ -103,6 +103,18 @@ class DmmRfOut(ctypes.Structure):
     _fields_ = [(n, _P) for n in ("s", "s_x", "s_y", "s_xx", "s_xy", "s_yy")]
 
 
+class DmmJetOut(ctypes.Structure):
+    """mmpde_dmm_jet_out / mmpde_dmm_jet_cot: the six [n_grid] arrays of the jet (or their cotangents), all
+    nullable."""
+    _fields_ = [(n, _P) for n in ("phi", "phi_x", "phi_y", "phi_xx", "phi_xy", "phi_yy")]
+
+
+class DmmJetGrads(ctypes.Structure):
+    """mmpde_dmm_jet_grads: the outputs of mmpde_dmm_jet_grad, all required."""
+    _fields_ = [(n, _P) for n in ("d_branch", "d_t0_w", "d_t0_b", "d_t1_w", "d_t1_b", "d_o0_w", "d_o0_b",
+                                  "d_o1_w", "d_o1_b")]
+
+
 class RfProblem(ctypes.Structure):
     """mmpde_rf_problem: the tables and sample of mmpde_rf_objective."""
     _fields_ = [(n, _P) for n in ("so_x", "so_y", "so_xx", "so_xy", "so_yy", "b_x0", "b_x1", "b_y0", "b_y1",
@@ -243,6 +255,9 @@ _SIGS = {
     "mmpde_dmm_phi": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "mmpde_dmm_rf_features_workspace_bytes": (_I64, [_I64, _I64, _I, _I, _I]),
     "mmpde_dmm_rf_features": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P]),
+    "mmpde_dmm_jet_workspace_bytes": (_I64, [_I64, _I64, _I, _I, _I]),
+    "mmpde_dmm_jet": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
+    "mmpde_dmm_jet_grad": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "mmpde_rf_objective_workspace_bytes": (_I64, [_I64, _I64]),
     "mmpde_rf_objective": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "mmpde_sym_matvec": (_I, [_P, _P, _I, _P, _F, _P]),
@@ -285,7 +300,7 @@ def lib():
             except AttributeError:
                 # an entry added without a version step (mmpde_dmm_mesh_relax, mmpde_mesh_quality, mmpde_itp_*_net,
                 # the random-feature phase's mmpde_dmm_rf_features / mmpde_rf_objective / mmpde_sym_matvec /
-                # mmpde_bfgs_update in 12302)
+                # mmpde_bfgs_update, the training jet's mmpde_dmm_jet / mmpde_dmm_jet_grad in 12302)
                 raise HipExtensionMissing(
                     f"{LIB_PATH} (ABI {h.mmpde_version()}) does not export {name}: it was built "
                     f"from an older tree; rebuild it with __graft_entry__.build()") from None

@@ -134,6 +134,42 @@ class GNN_Layer_FS_2D(nn.Module):  # noqa: N801 - reference name
         return self.norm(x + self.update_net_2(self.update_net_1(torch.cat((x, m), dim=-1))))
 
 
+class _HeadJet(torch.autograd.Function):
+    """DMM.jet's kernel pair: mmpde_dmm_jet forward, mmpde_dmm_jet_grad backward.
+    Differentiable, first order, in branch and the head's tensors; the grid rows
+    are data.  Only the inputs are saved: the backward recomputes the head."""
+
+    @staticmethod
+    def forward(ctx, branch, grid, second_order, dims, t0_w, t0_b, t1_w, t1_b, o0_w, o0_b, o1_w, o1_b):
+        head = [L.f32c(t) for t in (t0_w, t0_b, t1_w, t1_b, o0_w, o0_b, o1_w)]
+        hd = _head_struct(head, dims)
+        out = ops.dmm_jet(branch, grid, hd, o1_b, second_order)
+        ctx.save_for_backward(branch, grid, *head)
+        ctx.dims = dims
+        ctx.has_bias = o1_b is not None
+        ctx.set_materialize_grads(False)   # an unused output's cotangent stays None: a null pointer, zero
+        res = tuple(t.reshape(-1, 1) for t in out if t is not None)
+        return res
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *cots):
+        branch, grid, *head = ctx.saved_tensors
+        hd = _head_struct(head, ctx.dims)
+        g = ops.dmm_jet_grad(branch, grid, hd, cots)
+        # phi's bias reaches the loss through phi alone: no gradient (not a zero one) when phi is unused, as on
+        # the autograd route, so that an optimiser with weight decay leaves it alone
+        return (g.branch, None, None, None, g.t0_w, g.t0_b, g.t1_w, g.t1_b, g.o0_w, g.o0_b, g.o1_w,
+                g.o1_b if ctx.has_bias and cots[0] is not None else None)
+
+
+def _head_struct(fh, dims):
+    """_lib.DmmHead over the seven float32 head tensors fh (kept alive by the caller); dims = (th, L, L')."""
+    th, latent, hidden = dims
+    return L.DmmHead(fh[0].data_ptr(), fh[1].data_ptr(), fh[2].data_ptr(), fh[3].data_ptr(), th, latent,
+                     fh[4].data_ptr(), fh[5].data_ptr(), fh[6].data_ptr(), hidden)
+
+
 class DMM(nn.Module):
     """Reference dmm_model.py:145-219."""
 
@@ -341,6 +377,34 @@ class DMM(nn.Module):
             out = ops.dmm_rf_features(branch, grid, hd, second_order)
         del keep
         return out
+
+    def jet(self, u: torch.Tensor, grid: torch.Tensor, second_order: bool = True,
+            branch: torch.Tensor | None = None):
+        """phi = forward(u, grid) and its derivatives in the grid row -- the jet
+        (phi, phi_x, phi_y, phi_xx, phi_xy, phi_yy) the Monge-Ampere loss is made
+        of -- from the head's closed form (ops.dmm_jet) instead of autograd
+        through out_nn: what the reference's Adam and LBFGS phases obtain with
+        autograd.grad(create_graph=True) twice (mesh/dmm_utils.py:507-552).
+        u, grid as for forward; branch: the branch output [B, L] to use instead
+        of computing it from u.  In train() the branch comes from the torch ops
+        of the train()-mode forward (_branch_train): it stays differentiable and
+        the graph branch's BatchNorms advance their running statistics once per
+        call; in eval() it is branch_features(u).  The outputs are differentiable,
+        first order, in the branch and in the head's parameters (trunk, out_nn);
+        not in grid, which must not require grad.
+        Returns ops.Jet of six [rows, 1] tensors, the last three None with
+        second_order=False."""
+        L.require_device(u, grid)
+        if grid.requires_grad:
+            raise ValueError("DMM.jet is not differentiable in grid: pass the rows detached (the derivatives in "
+                             "the row are the jet's outputs)")
+        self._head_params()   # NotImplementedError for a head the kernels do not take
+        if branch is None:
+            branch = self._branch_train(u) if self.training else self.branch_features(u)
+        tl, ol = self.trunk.layers, self.out_nn.layers
+        dims = (tl[0].out_features, tl[1].out_features, ol[0].out_features)
+        out = _HeadJet.apply(branch, grid, bool(second_order), dims, *self._tensors()[0], ol[1].bias)
+        return ops.Jet(*out, *([None] * (6 - len(out))))
 
     def grid_nbr(self, grid: torch.Tensor, k: int = 35) -> torch.Tensor:
         """kNN-35 table of the fixed grid (reference dmm_model.py:222-234 builds it

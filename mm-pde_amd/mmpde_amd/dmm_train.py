@@ -24,7 +24,10 @@ optimiser is mmpde_amd.minimize.minimize_bfgs.  Three stated differences:
 What runs where:
 * the DMM forward in train() mode: differentiable device torch ops
   (dmm_model.DMM._forward_train), so grad(phi) and its second derivatives
-  come from autograd exactly as in the reference;
+  come from autograd exactly as in the reference; with jet=True the head's
+  part of that -- phi's jet and its gradient in the branch output and the head
+  parameters -- is the kernel pair mmpde_dmm_jet / mmpde_dmm_jet_grad (DMM.jet)
+  and only the branch stays torch;
 * the softmax kernel smoother -- the reference's ``interpolate`` /
   ``interpolate_tri``, which materialise [queries, points] tensors with the
   value field repeated per query -- on the HIP kernel mmpde_softmax_interp,
@@ -253,14 +256,21 @@ def _grad(out, x):
                                create_graph=True, allow_unused=True)[0]
 
 
-def boundary_loss(model, bounds, bound_us):
+def boundary_loss(model, bounds, bound_us, jet: bool = False):
     """Soft boundary condition (dmm_utils.py:441-503): d phi / dx = 0 on x = 0, 1
-    and d phi / dy = 0 on y = 0, 1, mean of the four MSEs."""
+    and d phi / dy = 0 on y = 0, 1, mean of the four MSEs.  jet: the derivatives
+    from DMM.jet (first order, one model call per side, in the same order)
+    instead of autograd."""
     mse = nn.MSELoss()
     parts = []
     for side, (b, bu) in enumerate(zip(bounds, bound_us)):
         if len(b) == 0:
             parts.append(torch.zeros(1, device=b.device))
+            continue
+        if jet:
+            j = model.jet(bu, b.detach(), second_order=False)
+            d = j.phi_x if side < 2 else j.phi_y
+            parts.append(mse(d, torch.zeros_like(d)))
             continue
         c1, c2 = b[:, 0].view(-1, 1), b[:, 1].view(-1, 1)
         c1.requires_grad = True
@@ -271,28 +281,61 @@ def boundary_loss(model, bounds, bound_us):
     return sum(parts) / 4
 
 
-def ma_losses(model, u, ux, uy, alpha, rhs, x, nx, bound_constraint="soft", init_mesh=False):
+def _jet_derivatives(model, u, x1, x2, bound_constraint, second_order):
+    """(phix, phiy, phixx, phixy, phiyy) of the loss's phi at the rows (x1, x2)
+    from DMM.jet; the hard boundary ansatz x1^2 x2^2 (x1 - 1)^2 (x2 - 1)^2 phi +
+    x1^2 / 2 + x2^2 / 2 is applied to the jet by the product rule.  The last
+    three are None without second_order."""
+    j = model.jet(u, torch.cat((x1, x2), dim=1), second_order=second_order)
+    if bound_constraint == "soft":
+        return j.phi_x, j.phi_y, j.phi_xx, j.phi_xy, j.phi_yy
+
+    def poly(t):   # a = t^2 (t - 1)^2, a', a''
+        return (t ** 2) * ((t - 1) ** 2), 2 * t * (t - 1) * (2 * t - 1), 2 * (6 * t ** 2 - 6 * t + 1)
+
+    a, a1, a2 = poly(x1)
+    b, b1, b2 = poly(x2)
+    w, wx, wy = a * b, a1 * b, a * b1
+    phix = wx * j.phi + w * j.phi_x + x1
+    phiy = wy * j.phi + w * j.phi_y + x2
+    if not second_order:
+        return phix, phiy, None, None, None
+    phixx = a2 * b * j.phi + 2 * wx * j.phi_x + w * j.phi_xx + 1
+    phixy = a1 * b1 * j.phi + wx * j.phi_y + wy * j.phi_x + w * j.phi_xy
+    phiyy = a * b2 * j.phi + 2 * wy * j.phi_y + w * j.phi_yy + 1
+    return phix, phiy, phixx, phixy, phiyy
+
+
+def ma_losses(model, u, ux, uy, alpha, rhs, x, nx, bound_constraint="soft", init_mesh=False, jet: bool = False):
     """The interior terms of dmm_utils.py:507-552: phi at the sampled points (hard
     constraint: the boundary-shaped ansatz), grad(phi), and either the identity
     fit (init_mesh) or the Monge-Ampere residual of the moved points
     m(x + grad phi) det(I + Hess phi) / RHS - 1 with the convexity penalty.
+    jet: phi's derivatives from DMM.jet (one second-order call; phi_xy stands
+    for phi_yx) instead of nested autograd; everything after them is the same.
     Returns (loss_in, loss_convex or None, LHS or None)."""
     mse = nn.MSELoss()
     x1 = x[:, 0].view(x.shape[0], 1)
     x2 = x[:, 1].view(x.shape[0], 1)
-    x1.requires_grad = True
-    x2.requires_grad = True
-    xx = torch.cat((x1, x2), dim=1)
-    if bound_constraint == "soft":
-        out = model(u, xx)
+    if jet:
+        x1, x2 = x1.detach(), x2.detach()
+        phix, phiy, phixx, phixy, phiyy = _jet_derivatives(model, u, x1, x2, bound_constraint, not init_mesh)
+        phiyx = phixy
     else:
-        out = (x1 ** 2) * (x2 ** 2) * ((x1 - 1) ** 2) * ((x2 - 1) ** 2) * model(u, xx) \
-            + 0.5 * x1 ** 2 + 0.5 * x2 ** 2
-    phix, phiy = _grad(out, x1), _grad(out, x2)
+        x1.requires_grad = True
+        x2.requires_grad = True
+        xx = torch.cat((x1, x2), dim=1)
+        if bound_constraint == "soft":
+            out = model(u, xx)
+        else:
+            out = (x1 ** 2) * (x2 ** 2) * ((x1 - 1) ** 2) * ((x2 - 1) ** 2) * model(u, xx) \
+                + 0.5 * x1 ** 2 + 0.5 * x2 ** 2
+        phix, phiy = _grad(out, x1), _grad(out, x2)
     if init_mesh:
         return (mse(x1 + phix, x1) + mse(x2 + phiy, x2)) / 2, None, None
-    phixy, phixx = _grad(phix, x2), _grad(phix, x1)
-    phiyx, phiyy = _grad(phiy, x1), _grad(phiy, x2)
+    if not jet:
+        phixy, phixx = _grad(phix, x2), _grad(phix, x1)
+        phiyx, phiyy = _grad(phiy, x1), _grad(phiy, x2)
     # ux, uy of each field at its moved points (field f for points f nx .. f nx + nx - 1)
     uxm = interpolate(ux, x1 + phix, x2 + phiy)
     uym = interpolate(uy, x1 + phix, x2 + phiy)
@@ -318,16 +361,17 @@ def _sample(args, all_u, bx, bu, device):
     return u, ux, uy, alpha, rhs, x, bounds[:4], bounds[4:8]
 
 
-def objective(model, args, sample, nx, init_mesh, device):
+def objective(model, args, sample, nx, init_mesh, device, jet: bool = False):
     """One draw's total loss (dmm_utils.py:441-552): (loss, loss_in, loss_bound,
-    loss_convex, LHS, RHS)."""
+    loss_convex, LHS, RHS).  jet: phi's derivatives from DMM.jet (closed form,
+    hand-written backward) instead of nested autograd through the model."""
     u, ux, uy, alpha, rhs, x, bounds, bound_us = sample
     if args.bound_constraint == "soft":
-        loss_bound = boundary_loss(model, bounds, bound_us)
+        loss_bound = boundary_loss(model, bounds, bound_us, jet)
     else:
         loss_bound = torch.tensor(0).to(device)
     loss_in, loss_convex, lhs = ma_losses(model, u, ux, uy, alpha, rhs, x, nx, args.bound_constraint,
-                                          init_mesh)
+                                          init_mesh, jet)
     loss = args.loss_weight1 * loss_bound + args.loss_weight0 * loss_in
     if not init_mesh and args.loss_convex:
         loss = loss + args.loss_weight2 * loss_convex
@@ -389,7 +433,7 @@ def random_feature_epoch(model, args, all_u, device, dense=None):
 
 # --------------------------------------------------------------------------- training
 def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_epoch_lbfgs, device,
-                 save_dir=None, evaluate_every=1, reference_save_path=False):  # noqa: N802 - reference name
+                 save_dir=None, evaluate_every=1, reference_save_path=False, jet: bool = False):  # noqa: N802
     """dmm_utils.py:391-1095: n_epoch_adam
     epochs of Adam then n_epoch_lbfgs of LBFGS, each epoch max(1, train_sample_grid
     T / (bx bu)) draws of fresh samples; per epoch the equation residual of the
@@ -410,6 +454,11 @@ def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_e
     that the four lists stay the same length) -- the log lines, evaluate[_tri]
     and the checkpoint as in the other phases.  rf_opt_alg='Newton' raises
     NotImplementedError before any epoch runs.
+
+    jet=True takes phi's derivatives in both phases and in the random-feature
+    check pass from DMM.jet (mmpde_dmm_jet and its hand-written backward) instead
+    of autograd three deep through out_nn; the loss, the optimisers and the
+    logging are the same.  Default False: the autograd route, bit for bit.
 
     Checkpoint file: 'dmm_{experiment}_epoch{N}.pt' in save_dir, one per epoch;
     reference_save_path=True writes the reference's name instead,
@@ -502,7 +551,7 @@ def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_e
             if adam:
                 sample = _sample(args, all_u, bx, bu, device)
                 opt_adam.zero_grad()
-                loss, li, lb, lc, lhs, rhs = objective(model, args, sample, bx, init_mesh, device)
+                loss, li, lb, lc, lhs, rhs = objective(model, args, sample, bx, init_mesh, device, jet)
                 loss.backward()
                 record(0, li, lb, lc, lhs, rhs)
                 opt_adam.step()
@@ -510,7 +559,7 @@ def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_e
                 def closure():
                     sample = _sample(args, all_u, bx, bu, device)
                     opt_lbfgs.zero_grad()
-                    loss, li, lb, lc, lhs, rhs = objective(model, args, sample, bx, init_mesh, device)
+                    loss, li, lb, lc, lhs, rhs = objective(model, args, sample, bx, init_mesh, device, jet)
                     loss.backward()
                     record(1, li, lb, lc, lhs, rhs)
                     return loss
@@ -534,7 +583,7 @@ def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_e
         # the check pass (dmm_utils.py:950-1061): a fresh sample through the full model
         bx = args.batch_size_x_rf
         sample = _sample(args, all_u, bx, args.batch_size_u_rf, device)
-        _, li, lb, _, lhs, rhs = objective(model, args, sample, bx, False, device)
+        _, li, lb, _, lhs, rhs = objective(model, args, sample, bx, False, device, jet)
         equ_residual(lhs.detach(), rhs)
         log["loss_in"].append(li.item())
         log["loss_bound"].append(lb.item())

@@ -969,6 +969,81 @@ def dmm_rf_features(branch: torch.Tensor, grid: torch.Tensor, head_params, secon
     return RfFeatures(*tabs)
 
 
+Jet = collections.namedtuple("Jet", ("phi", "phi_x", "phi_y", "phi_xx", "phi_xy", "phi_yy"))
+Jet.__doc__ = """The Monge-Ampere jet of the DMM head per grid row: phi and its derivatives in the row;
+phi_xx, phi_xy, phi_yy are None with second_order=False."""
+JetGrads = collections.namedtuple("JetGrads", ("branch", "t0_w", "t0_b", "t1_w", "t1_b", "o0_w", "o0_b", "o1_w",
+                                               "o1_b"))
+JetGrads.__doc__ = """ops.dmm_jet_grad's gradients: of branch [B, L] and of trunk.layers[0/1] and
+out_nn.layers[0/1] weight and bias, each in its parameter's shape."""
+
+
+def _jet_args(branch, grid, hd, workspace):
+    L.require_device(branch, grid)
+    branch = L.f32c(branch)
+    grid = L.f32c(grid).reshape(-1, 2)
+    if branch.dim() != 2 or branch.shape[1] != hd.latent:
+        raise ValueError("branch must be [B, L]")
+    B, ng = branch.shape[0], grid.shape[0]
+    if B < 1 or ng < 1 or ng % B:
+        raise ValueError("grid rows must be a multiple of the batch size")
+    nb = L.lib().mmpde_dmm_jet_workspace_bytes(B, ng, hd.latent, hd.hidden, hd.th)
+    if workspace is None:
+        workspace = torch.empty((max(nb, 16) // 4,), dtype=torch.float32, device=grid.device)
+    else:
+        L.require_device(workspace)
+        if workspace.numel() * workspace.element_size() < nb:
+            raise ValueError("workspace is smaller than mmpde_dmm_jet_workspace_bytes")
+    return branch, grid, B, ng, workspace
+
+
+def dmm_jet(branch: torch.Tensor, grid: torch.Tensor, head_params, o1_b: torch.Tensor | None = None,
+            second_order: bool = True, workspace: torch.Tensor | None = None) -> Jet:
+    """mmpde_dmm_jet: phi = out_nn(cat(branch_b, trunk(grid_i))) and its first and
+    second derivatives in the grid row, [n_grid] each, in closed form (no
+    autograd, no [n_grid, L'] table).  branch [B, L], grid [n_grid, 2] (row i
+    belongs to trajectory i // (n_grid // B)), head_params: the model's
+    _lib.DmmHead, o1_b: out_nn's last bias (None: 0).  With second_order=False
+    the first-order outputs keep their bits.  No synchronisation; capturable
+    given a workspace."""
+    hd = head_params
+    branch, grid, B, ng, workspace = _jet_args(branch, grid, hd, workspace)
+    outs = [torch.empty((ng,), dtype=torch.float32, device=grid.device)
+            for _ in range(6 if second_order else 3)] + [None] * (0 if second_order else 3)
+    out = L.DmmJetOut(*[L.ptr(t) for t in outs])
+    ob = L.f32c(o1_b) if o1_b is not None else None
+    L.check(L.lib().mmpde_dmm_jet(L.ptr(branch), B, L.ptr(grid), ng, ctypes.byref(hd), L.ptr(ob),
+                                  L.ptr(workspace), ctypes.byref(out), L.stream(grid.device)), "mmpde_dmm_jet")
+    return Jet(*outs)
+
+
+def dmm_jet_grad(branch: torch.Tensor, grid: torch.Tensor, head_params, cotangents,
+                 workspace: torch.Tensor | None = None) -> JetGrads:
+    """mmpde_dmm_jet_grad: the gradient of sum_c <cotangents[c], jet_c> in branch
+    and the head's seven tensors and last bias.  cotangents: six [n_grid]
+    tensors in Jet's order, None meaning zero.  The grid rows are data: no
+    gradient in them.  Sums in a fixed order: the same bits on every call."""
+    hd = head_params
+    branch, grid, B, ng, workspace = _jet_args(branch, grid, hd, workspace)
+    cots = []
+    for c in tuple(cotangents) + (None,) * (6 - len(cotangents)):
+        if c is not None:
+            L.require_device(c)
+            c = L.f32c(c).reshape(-1)
+            if c.numel() != ng:
+                raise ValueError("a cotangent must have one value per grid row")
+        cots.append(c)
+    dev = grid.device
+    Lt, Lp, th = hd.latent, hd.hidden, hd.th
+    g = JetGrads(*[torch.empty(s, dtype=torch.float32, device=dev)
+                   for s in ((B, Lt), (th, 2), (th,), (Lt, th), (Lt,), (Lp, 2 * Lt), (Lp,), (1, Lp), (1,))])
+    cot = L.DmmJetOut(*[L.ptr(c) for c in cots])
+    gr = L.DmmJetGrads(*[L.ptr(t) for t in g])
+    L.check(L.lib().mmpde_dmm_jet_grad(L.ptr(branch), B, L.ptr(grid), ng, ctypes.byref(hd), None, L.ptr(workspace),
+                                       ctypes.byref(cot), ctypes.byref(gr), L.stream(dev)), "mmpde_dmm_jet_grad")
+    return g
+
+
 class RfObjective:
     """random_feature_torch2 (mesh/dmm_utils.py:351-388) and its gradient on
     mmpde_rf_objective: f(w) = convex_rel (sum w^2)^2 + w1 loss_bound + w0 loss_in
