@@ -1135,6 +1135,63 @@ int mmpde_sym_matvec(const float *H, const float *g, int n, float *d_out, float 
 int64_t mmpde_bfgs_update_workspace_bytes(int n);
 int mmpde_bfgs_update(float *H, const float *s, const float *y, int n, void *workspace, mmpde_stream_t stream);
 
+/* The graph branch of DMM in train() mode (reference mesh/dmm_model.py:94-142,
+ * 197-210 under model.train()): one tanh GNN layer of hidden width 4 and the
+ * decoding DenseNet [4, 128, 1], forward and backward.  The residual add, the
+ * BatchNorms on batch statistics (mmpde_batch_norm_rows_train), the embedding
+ * and output_mlp (the row kernels) are the caller's.
+ *
+ * Layer, for B trajectories of n_per nodes sharing one [n_per, k] table of
+ * LOCAL sources (any k >= 1; an entry outside [0, n_per) is read as n_per - 1):
+ *     upd_i = tanh(U2 tanh(U1 cat(h_i, mean_j M2 tanh(M1 cat(h_i, h_j, u_i - u_j,
+ *             g_i - g_j)))))                                  [B n_per, 4]
+ * h [B n_per, 4], u [B n_per], grid [n_per, 2]; msg1_w [4, 11], msg2_w, upd2_w
+ * [4, 4], upd1_w [4, 8], every bias [4].
+ * mmpde_dmm_gnn_train_backward: from d_upd = dL/d upd it overwrites d_h with the
+ * layer's own dL/dh (target and source sides; u and grid are data) and grads
+ * [MMPDE_DMM_GNN_TRAIN_GRADS] with the eight parameter gradients in the order
+ * msg1_w 44, msg1_b 4, msg2_w 16, msg2_b 4, upd1_w 32, upd1_b 4, upd2_w 16,
+ * upd2_b 4.  rev_off [n_per + 1], rev_edge: mmpde_reverse_adjacency of the
+ * table (n_src = n_tgt = n_per, no degrees).  Nothing of the forward is kept:
+ * the backward recomputes the layer from h.  workspace >=
+ * mmpde_dmm_gnn_train_workspace_bytes(B, n_per, k), 16-B aligned: dL/dm [B n_per,
+ * 4], one partial row of gradients per workgroup (B ceil(n_per / 128)) and the
+ * per-edge message-net delta [B n_per k, 4], the only per-edge array.
+ *
+ * Decoder: out[i] = w1 . tanh(w0 h_i + b0) + b1 (w0 [128, 4], b0, w1 [128], b1
+ * [1]); the backward overwrites d_h [n_tot, 4] and grads
+ * [MMPDE_DMM_DECODE_TRAIN_GRADS] = d_w0 512, d_b0 128, d_w1 128, d_b1 1.
+ * workspace >= mmpde_dmm_decode_train_workspace_bytes(n_tot), 16-B aligned (one
+ * partial row per 1024 nodes); no [n_tot, 128] table is held.
+ *
+ * Every sum runs in a fixed order, no atomics: two calls on the same inputs
+ * give the same bits, and a trajectory's rows do not depend on its batch.
+ * Stream-ordered, no allocation, no synchronisation.  Refused before any launch:
+ * a null or misaligned pointer, B < 1, n_per < 1 (MMPDE_ERR_INVALID_ARG);
+ * hidden != 4, k < 1, B > 65535 (MMPDE_ERR_UNSUPPORTED).  The workspace sizes
+ * are 0 for a non-positive argument.  Added without a version step. */
+#define MMPDE_DMM_GNN_TRAIN_GRADS 124
+#define MMPDE_DMM_DECODE_TRAIN_GRADS 769
+typedef struct {
+    const float *msg1_w, *msg1_b, *msg2_w, *msg2_b, *upd1_w, *upd1_b, *upd2_w, *upd2_b;
+} mmpde_dmm_gnn_weights;
+int64_t mmpde_dmm_gnn_train_workspace_bytes(int64_t batches, int64_t n_per, int k);
+int mmpde_dmm_gnn_train_forward(const float *h, const float *u, const float *grid, int64_t batches,
+                                int64_t n_per, const int32_t *nbr, int k, int hidden,
+                                const mmpde_dmm_gnn_weights *w, float *upd, mmpde_stream_t stream);
+int mmpde_dmm_gnn_train_backward(const float *h, const float *u, const float *grid, int64_t batches,
+                                 int64_t n_per, const int32_t *nbr, int k, int hidden,
+                                 const int64_t *rev_off, const int64_t *rev_edge,
+                                 const mmpde_dmm_gnn_weights *w, const float *d_upd, float *d_h,
+                                 float *grads, void *workspace, mmpde_stream_t stream);
+int64_t mmpde_dmm_decode_train_workspace_bytes(int64_t n_tot);
+int mmpde_dmm_decode_train_forward(const float *h, int64_t n_tot, int hidden, const float *w0,
+                                   const float *b0, const float *w1, const float *b1, float *out,
+                                   mmpde_stream_t stream);
+int mmpde_dmm_decode_train_backward(const float *h, int64_t n_tot, int hidden, const float *w0,
+                                    const float *b0, const float *w1, const float *d_out, float *d_h,
+                                    float *grads, void *workspace, mmpde_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Mesh quality of a moved mesh (reference mesh/dmm_utils.py:1162-1284,
  * evaluate_tri / evaluate), batched and per trajectory

@@ -205,6 +205,9 @@ class DMM(nn.Module):
         self._pack_key = None
         self._pack = None
         self._grid_cache = {}
+        self._rev_cache = {}
+        # train() mode, graph branch: run _branch_train on the HIP kernels (a plain attribute, not in state_dict)
+        self.hip_branch_train = False
 
     def forward(self, u, grid, rf=False):
         """dmm_model.py:185-219: phi = out_nn(cat(branch(u), trunk(grid))), the
@@ -252,17 +255,25 @@ class DMM(nn.Module):
             return out
         return out, second, torch.ones_like(second).reshape(-1, 1)
 
-    def _branch_train(self, u):
+    def _branch_train(self, u, nbr=None):
         """The branch of _forward_train [B, L] (dmm_model.py:188,197-210 in train()
         mode): the graph branch's BatchNorms use batch statistics and advance
-        their running statistics once per call."""
+        their running statistics once per call.  nbr: graph mode only, an [N, k]
+        int32 local neighbour table used instead of the kNN-35 table of
+        self.ori_grid.  With hip_branch_train the graph branch runs on the HIP
+        kernels (_branch_train_hip); the array branch ignores the flag."""
         B = u.shape[0]
         if self.mode == "array":
+            if nbr is not None:
+                raise ValueError("nbr is a graph-mode argument")
             return self.branch(u.unsqueeze(1))
         else:
             og = torch.as_tensor(self.ori_grid).to(u.device, torch.float32).reshape(-1, 2)
             N = og.shape[0]
-            nbr = self.grid_nbr(og.contiguous())                       # [N, 35] local
+            og = og.contiguous()
+            nbr = self.grid_nbr(og) if nbr is None else self._local_nbr(nbr, N, u.device)   # [N, 35] local
+            if self.hip_branch_train:
+                return self._branch_train_hip(u, og, nbr)
             gnbr = (nbr[None].long() + N * torch.arange(B, device=u.device)[:, None, None])
             gnbr = gnbr.reshape(B * N, -1)
             x = u.reshape(-1, 1)
@@ -273,6 +284,51 @@ class DMM(nn.Module):
                 h = layer(h, x, pos_x, pos_y, gnbr)
             h, _ = self.decoding_mlp(h)
             return self.output_mlp(h.reshape(B, -1))
+
+    def _branch_train_hip(self, u, og, nbr):
+        """_branch_train's graph branch on kernels, forward and backward: the
+        embedding on the row kernels (ops.linear_train, ops.batch_norm_rows),
+        every GNN layer's update on ops.DmmGnnLayerTrain with its residual and
+        BatchNorm on ops.batch_norm_rows, the decoder on ops.DmmDecodeTrain,
+        output_mlp on the few-row skinny kernels (ops.FewRowsMlp; above 4096
+        trajectories on ops.linear_train).  The same modules' BatchNorms advance
+        in the same order as on the torch route; no per-edge tensor and no
+        library GEMM."""
+        if self.hidden_features != 4:
+            raise NotImplementedError("hip_branch_train: the graph branch kernels take hidden_features == 4 only "
+                                      f"(got {self.hidden_features})")
+        L.require_device(u)
+        B, N = u.shape[0], og.shape[0]
+        rev = self._nbr_rev(nbr)
+        uf = u.float().reshape(-1)
+        e = self.embedding_mlp
+        x3 = torch.cat((uf[:, None], og.repeat(B, 1)), -1)
+        h = ops.batch_norm_rows(e[1], ops.linear_train(x3, e[0]))
+        h = ops.batch_norm_rows(e[4], ops.linear_train(torch.tanh(h), e[3]))
+        for g in self.gnn_layers:
+            upd = ops.DmmGnnLayerTrain.apply(
+                h, uf, og, nbr, rev, g.message_net_1[0].weight, g.message_net_1[0].bias, g.message_net_2[0].weight,
+                g.message_net_2[0].bias, g.update_net_1[0].weight, g.update_net_1[0].bias, g.update_net_2[0].weight,
+                g.update_net_2[0].bias)
+            h = ops.batch_norm_rows(g.norm.module, upd, res=h)
+        d = self.decoding_mlp.layers
+        dec = ops.DmmDecodeTrain.apply(h, d[0].weight, d[0].bias, d[1].weight, d[1].bias)
+        o = self.output_mlp
+        x = dec.reshape(B, N)
+        if B <= 4096:     # a few rows of K = N: the split-K skinny kernels (the row GEMMs take the shape, slowly)
+            return ops.FewRowsMlp.apply(x, o[0].weight, o[0].bias, o[2].weight, o[2].bias, o[4].weight, o[4].bias)
+        x = torch.tanh(ops.linear_train(x, o[0]))
+        x = torch.tanh(ops.linear_train(x, o[2]))
+        return ops.linear_train(x, o[4])
+
+    def _nbr_rev(self, nbr: torch.Tensor):
+        """ops.reverse_adjacency of a local table, built (and range-checked) once per table."""
+        key = (nbr.data_ptr(), nbr._version, tuple(nbr.shape), str(nbr.device))
+        hit = self._rev_cache.get(key)
+        if hit is None:
+            hit = (nbr, ops.reverse_adjacency(nbr))   # holds the table: its storage cannot be reused meanwhile
+            self._rev_cache = {key: hit}
+        return hit[1]
 
     # ----------------------------------------------------------------- packing
     def _check(self):

@@ -433,7 +433,8 @@ def random_feature_epoch(model, args, all_u, device, dense=None):
 
 # --------------------------------------------------------------------------- training
 def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_epoch_lbfgs, device,
-                 save_dir=None, evaluate_every=1, reference_save_path=False, jet: bool = False):  # noqa: N802
+                 save_dir=None, evaluate_every=1, reference_save_path=False, jet: bool = False,
+                 hip_branch: bool = False):  # noqa: N802
     """dmm_utils.py:391-1095: n_epoch_adam
     epochs of Adam then n_epoch_lbfgs of LBFGS, each epoch max(1, train_sample_grid
     T / (bx bu)) draws of fresh samples; per epoch the equation residual of the
@@ -460,6 +461,12 @@ def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_e
     of autograd three deep through out_nn; the loss, the optimisers and the
     logging are the same.  Default False: the autograd route, bit for bit.
 
+    hip_branch=True runs the train-mode graph branch (cylinder) on the HIP
+    kernels for the run (DMM.hip_branch_train, restored afterwards): the GNN
+    layers and the decoder on mmpde_dmm_gnn_train_* / mmpde_dmm_decode_train_*,
+    the BatchNorms, the embedding and output_mlp on the row kernels.  The array
+    branch (burgers) ignores it.  Default False: the torch ops, bit for bit.
+
     Checkpoint file: 'dmm_{experiment}_epoch{N}.pt' in save_dir, one per epoch;
     reference_save_path=True writes the reference's name instead,
     '{experiment}/{datetime}_{rf}_bound{loss_bound_rf}_..._{gamma_adam}'
@@ -473,6 +480,18 @@ def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_e
     init_mesh LBFGS phase runs backward like every other phase and logs 0 for
     the convexity loss and None for LHS (tests/test_gpu_dmm_train.py
     ::test_init_mesh_lbfgs_phase_trains)."""
+    prev = getattr(model, "hip_branch_train", False)
+    model.hip_branch_train = bool(hip_branch)
+    try:
+        return _train_ma_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_epoch_lbfgs, device,
+                             save_dir, evaluate_every, reference_save_path, jet)
+    finally:
+        model.hip_branch_train = prev
+
+
+def _train_ma_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_epoch_lbfgs, device, save_dir,
+                  evaluate_every, reference_save_path, jet):
+    """train_MA_res's epochs (the hip_branch flag already set on the model)."""
     model.train()
     opt_adam = torch.optim.Adam(model.parameters(), lr=args.lr_adam, betas=(0.9, 0.999), eps=1e-8,
                                 weight_decay=args.weight_decay)

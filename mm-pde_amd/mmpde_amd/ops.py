@@ -1044,6 +1044,167 @@ def dmm_jet_grad(branch: torch.Tensor, grid: torch.Tensor, head_params, cotangen
     return g
 
 
+def _gnn_weights(ws):
+    return L.DmmGnnWeights(*[t.data_ptr() for t in ws])
+
+
+class DmmGnnLayerTrain(torch.autograd.Function):
+    """The update of one train-mode DMM GNN layer (GNN_Layer_FS_2D of
+    dmm_model.py, hidden 4): upd = update_net_2(update_net_1(cat(h, mean of
+    message_net_2(message_net_1(cat(h_i, h_j, u_i - u_j, g_i - g_j))))))
+    [B N, 4], before the residual and the BatchNorm, on
+    mmpde_dmm_gnn_train_forward / _backward.  h [B N, 4], u [B N], grid [N, 2],
+    nbr [N, k] int32 local, rev = ops.reverse_adjacency(nbr) of the same table,
+    then the eight tensors of message_net_1/2 and update_net_1/2.  Gradients for
+    h and the eight tensors (u, the grid and the table are data); only the
+    inputs are saved -- the backward recomputes the layer -- and nothing per
+    edge outlives a call.  Deterministic."""
+
+    @staticmethod
+    def forward(ctx, h, u, grid, nbr, rev, *params):
+        L.require_device(h, u, grid, nbr, *rev, *params)
+        h, u, grid = L.f32c(h), L.f32c(u).reshape(-1), L.f32c(grid).reshape(-1, 2)
+        ws = [L.f32c(t) for t in params]
+        n, k = nbr.shape
+        nt, hidden = h.shape
+        if len(ws) != 8 or grid.shape[0] != n or nt % n or u.numel() != nt or nbr.dtype != torch.int32:
+            raise ValueError("DmmGnnLayerTrain: h [B N, C], u [B N], grid [N, 2], nbr [N, k] int32, eight tensors")
+        nbr = nbr.contiguous()
+        upd = torch.empty_like(h)
+        wp = _gnn_weights(ws)
+        L.check(L.lib().mmpde_dmm_gnn_train_forward(L.ptr(h), L.ptr(u), L.ptr(grid), nt // n, n, L.ptr(nbr), k, hidden,
+                                                    ctypes.byref(wp), L.ptr(upd), L.stream(h.device)),
+                "mmpde_dmm_gnn_train_forward")
+        ctx.save_for_backward(h, u, grid, nbr, rev[0], rev[1], *ws)
+        ctx.shapes = [tuple(t.shape) for t in params]
+        return upd
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_upd):
+        h, u, grid, nbr, rev_off, rev_edge, *ws = ctx.saved_tensors
+        d_upd = L.f32c(d_upd)
+        n, k = nbr.shape
+        nt, hidden = h.shape
+        dev = h.device
+        d_h = torch.empty_like(h)
+        grads = torch.empty((L.DMM_GNN_TRAIN_GRADS,), dtype=torch.float32, device=dev)
+        nb = L.lib().mmpde_dmm_gnn_train_workspace_bytes(nt // n, n, k)
+        wk = torch.empty((nb // 4,), dtype=torch.float32, device=dev)
+        wp = _gnn_weights(ws)
+        L.check(L.lib().mmpde_dmm_gnn_train_backward(
+            L.ptr(h), L.ptr(u), L.ptr(grid), nt // n, n, L.ptr(nbr), k, hidden, L.ptr(rev_off), L.ptr(rev_edge),
+            ctypes.byref(wp), L.ptr(d_upd), L.ptr(d_h), L.ptr(grads), L.ptr(wk), L.stream(dev)),
+            "mmpde_dmm_gnn_train_backward")
+        out, o = [], 0
+        for j, shp in enumerate(ctx.shapes):
+            cnt = math.prod(shp)
+            out.append(grads[o:o + cnt].view(shp) if ctx.needs_input_grad[5 + j] else None)
+            o += cnt
+        return (d_h if ctx.needs_input_grad[0] else None, None, None, None, None, *out)
+
+
+class DmmDecodeTrain(torch.autograd.Function):
+    """decoding_mlp = DenseNet[4, 128, 1] of the DMM graph branch in train mode:
+    d [n, 1] = w1 tanh(w0 h + b0) + b1 on mmpde_dmm_decode_train_forward, and
+    dL/dh with the four parameter gradients on _backward.  Only the inputs are
+    saved; no [n, 128] table is held in either direction.  Deterministic."""
+
+    @staticmethod
+    def forward(ctx, h, w0, b0, w1, b1):
+        L.require_device(h, w0, b0, w1, b1)
+        h = L.f32c(h)
+        ws = [L.f32c(t) for t in (w0, b0, w1, b1)]
+        n, hidden = h.shape
+        if tuple(ws[0].shape) != (128, hidden) or ws[1].numel() != 128 or ws[2].numel() != 128 or ws[3].numel() != 1:
+            raise ValueError("DmmDecodeTrain: DenseNet[C, 128, 1] only")
+        out = torch.empty((n, 1), dtype=torch.float32, device=h.device)
+        L.check(L.lib().mmpde_dmm_decode_train_forward(L.ptr(h), n, hidden, *[L.ptr(t) for t in ws], L.ptr(out),
+                                                       L.stream(h.device)), "mmpde_dmm_decode_train_forward")
+        ctx.save_for_backward(h, *ws[:3])
+        ctx.shapes = [tuple(t.shape) for t in (w0, b0, w1, b1)]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        h, w0, b0, w1 = ctx.saved_tensors
+        d_out = L.f32c(d_out).reshape(-1)
+        n, hidden = h.shape
+        dev = h.device
+        d_h = torch.empty_like(h)
+        grads = torch.empty((L.DMM_DECODE_TRAIN_GRADS,), dtype=torch.float32, device=dev)
+        nb = L.lib().mmpde_dmm_decode_train_workspace_bytes(n)
+        wk = torch.empty((nb // 4,), dtype=torch.float32, device=dev)
+        L.check(L.lib().mmpde_dmm_decode_train_backward(L.ptr(h), n, hidden, L.ptr(w0), L.ptr(b0), L.ptr(w1),
+                                                        L.ptr(d_out), L.ptr(d_h), L.ptr(grads), L.ptr(wk),
+                                                        L.stream(dev)), "mmpde_dmm_decode_train_backward")
+        out, o = [], 0
+        for j, shp in enumerate(ctx.shapes):
+            cnt = math.prod(shp)
+            out.append(grads[o:o + cnt].view(shp) if ctx.needs_input_grad[1 + j] else None)
+            o += cnt
+        return (d_h if ctx.needs_input_grad[0] else None, *out)
+
+
+class FewRowsMlp(torch.autograd.Function):
+    """A tanh MLP (tanh on all but the last Linear) over a few rows in train
+    mode -- the DMM graph branch's output_mlp at M = B trajectories, [B, N] ->
+    512 -> 256 -> L: the forward on mmpde_linear_skinny (split-K, tanh fused),
+    the backward per layer dW = dZ^T X, db = sum dZ (mmpde_outer_rows), dX = dZ W
+    as the skinny forward of W^T (mmpde_transpose), times tanh' of the layer
+    input (mmpde_tanh_bwd), as interpolate.ResCutMlp does for the cylinder
+    ``down`` MLP.  Arguments: x [M, K] (M <= 4096), then weight, bias per layer.
+    The row GEMMs of LinearRows tile 32 rows at a time and leave most of the
+    chip idle at M = 160 and K = 2521.  Exact fp32 products in fixed orders:
+    deterministic."""
+
+    @staticmethod
+    def forward(ctx, x, *params):
+        L.require_device(x, *params)
+        ws, bs = params[0::2], params[1::2]
+        ins = [L.f32c(x)]
+        for i, (w, b) in enumerate(zip(ws, bs)):
+            ins.append(linear_skinny(ins[-1], w, b, L.ACT_TANH if i + 1 < len(ws) else L.ACT_NONE))
+        y = ins.pop()
+        ctx.save_for_backward(*ins, *[L.f32c(w) for w in ws])
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        saved = ctx.saved_tensors
+        nl = len(saved) // 2
+        ins, ws = saved[:nl], saved[nl:]
+        lib = L.lib()
+        dev = dy.device
+        st = L.stream(dev)
+        grads = [None] * (2 * nl)
+        g = L.f32c(dy)
+        m = g.shape[0]
+        for layer in range(nl - 1, -1, -1):
+            w, xin = ws[layer], ins[layer]
+            n, k = w.shape
+            need_w, need_b = ctx.needs_input_grad[1 + 2 * layer], ctx.needs_input_grad[2 + 2 * layer]
+            if need_w or need_b:
+                dw = torch.empty((n, k), dtype=torch.float32, device=dev)
+                db = torch.empty((n,), dtype=torch.float32, device=dev) if need_b else None
+                L.check(lib.mmpde_outer_rows(L.ptr(g), n, L.ptr(xin), k, m, n, k, L.ptr(dw), k, L.ptr(db), st),
+                        "mmpde_outer_rows")
+                grads[2 * layer] = dw if need_w else None
+                grads[2 * layer + 1] = db
+            if layer == 0 and not ctx.needs_input_grad[0]:
+                g = None
+                break
+            wt = torch.empty((k, n), dtype=torch.float32, device=dev)
+            L.check(lib.mmpde_transpose(L.ptr(w), n, k, k, L.ptr(wt), n, st), "mmpde_transpose")
+            dx = linear_skinny(g, wt)
+            if layer > 0:   # the layer's input is the previous layer's tanh output
+                L.check(lib.mmpde_tanh_bwd(L.ptr(dx), L.ptr(xin), dx.numel(), L.ptr(dx), st), "mmpde_tanh_bwd")
+            g = dx
+        return (g, *grads)
+
+
 class RfObjective:
     """random_feature_torch2 (mesh/dmm_utils.py:351-388) and its gradient on
     mmpde_rf_objective: f(w) = convex_rel (sum w^2)^2 + w1 loss_bound + w0 loss_in
