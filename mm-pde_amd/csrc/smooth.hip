@@ -104,9 +104,11 @@ __global__ __launch_bounds__(256) void softmax_interp_kernel(const float2 *__res
         const float o = a.zv / a.z;
         if (GRAD) {
             // sum_j w_j (v_j - o) d_j = (zvd - o zd) / z
+            // one point: its weight is 1 wherever the query lies, the gradient
+            // identically 0 (zvd - o zd leaves the rounding of v d otherwise)
             const float gg = g[q];
-            out[2 * q] = gg * (a.zvdx - o * a.zdx) / a.z;
-            out[2 * q + 1] = gg * (a.zvdy - o * a.zdy) / a.z;
+            out[2 * q] = n_pts == 1 ? 0.0f : gg * (a.zvdx - o * a.zdx) / a.z;
+            out[2 * q + 1] = n_pts == 1 ? 0.0f : gg * (a.zvdy - o * a.zdy) / a.z;
         } else {
             out[q] = o;
         }

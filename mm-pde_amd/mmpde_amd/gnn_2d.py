@@ -412,7 +412,8 @@ class GNN_Layer_FS_2D(nn.Module):  # noqa: N801 - reference name
         ws = torch.empty((4 * n * 128,), dtype=torch.float32, device=x.device)
         out = torch.empty((n, 128), dtype=torch.float32, device=x.device)
         p = self._params()
-        L.check(L.lib().mmpde_gnn_layer(L.ptr(L.f32c(x)), L.ptr(L.f32c(u).reshape(-1)), L.ptr(pos),
+        x, u = L.f32c(x), L.f32c(u)     # held until the launch: a copy freed earlier is the next copy's memory
+        L.check(L.lib().mmpde_gnn_layer(L.ptr(x), L.ptr(u), L.ptr(pos),
                                         n, nbr.shape[1], L.ptr(nbr), L.GnnScales(1.0, 1.0, 1.0),
                                         ctypes.byref(p), L.ptr(ws), L.ptr(out),
                                         L.stream(x.device)), "mmpde_gnn_layer")

@@ -573,8 +573,11 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, b, stride: int, pad: int, act: int,
     ow = (wd + 2 * pad - ks) // stride + 1
     y = torch.empty((bt, cout, oh, ow), dtype=torch.float32, device=x.device)
     res = L.f32c(residual) if residual is not None else None
-    L.check(L.lib().mmpde_conv2d_ex(L.ptr(x), bt, cin, h, wd, L.ptr(L.f32c(w)),
-                                    L.ptr(L.f32c(b)) if b is not None else None, cout, ks, stride,
+    # w and b are held until the launch: f32c copies a misaligned or strided
+    # tensor, and a copy freed before the next one is made is that one's memory
+    w = L.f32c(w)
+    b = L.f32c(b) if b is not None else None
+    L.check(L.lib().mmpde_conv2d_ex(L.ptr(x), bt, cin, h, wd, L.ptr(w), L.ptr(b), cout, ks, stride,
                                     pad, L.PAD_CIRCULAR if circular else L.PAD_ZEROS, L.ptr(res),
                                     int(res_after_act), act, L.ptr(y), L.stream(x.device)),
             "mmpde_conv2d_ex")
