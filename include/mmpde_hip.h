@@ -1192,6 +1192,48 @@ int mmpde_dmm_decode_train_backward(const float *h, int64_t n_tot, int hidden, c
                                     const float *b0, const float *w1, const float *d_out, float *d_h,
                                     float *grads, void *workspace, mmpde_stream_t stream);
 
+/* The array branch of DMM in train() mode (reference mesh/dmm_model.py:48-81
+ * under model.train(), layers == 7): ConvNet's convolution stack, forward and
+ * backward, for `batches` fields u [batches, s, s]:
+ *     x1 = tanh(c0(u))        1 -> 8,  5x5, stride 2, pad 2   [8,  o1, o1]
+ *     x2 = tanh(c1(x1))       8 -> 16, 5x5, stride 1, pad 2   [16, o1, o1]
+ *     x3 = tanh(x1 + c2(x2))  16 -> 8, 5x5, stride 1, pad 2   [8,  o1, o1]
+ *     f  = tanh(c3(x3))       8 -> 1,  5x5, stride 2, pad 2   [o2, o2]
+ * with o1 = (s - 1) / 2 + 1 and o2 = (o1 - 1) / 2 + 1; fc2 / fc3 are the
+ * caller's (the few-row kernels).  Weights as torch stores them: c0_w [8, 1, 5,
+ * 5], c1_w [16, 8, 5, 5], c2_w [8, 16, 5, 5], c3_w [1, 8, 5, 5] and the biases
+ * [8], [16], [8], [1], all required.
+ * mmpde_dmm_convnet_train_forward writes f [batches, o2 o2].
+ * mmpde_dmm_convnet_train_backward: from d_f = dL/df it overwrites grads
+ * [MMPDE_DMM_CONVNET_TRAIN_GRADS] with the eight parameter gradients in the
+ * order c0_w 200, c0_b 8, c1_w 3200, c1_b 16, c2_w 3200, c2_b 8, c3_w 200, c3_b
+ * 1; u is data.  Nothing of the forward is kept: the backward recomputes the
+ * stack from u.  workspace: at least
+ * mmpde_dmm_convnet_train_workspace_bytes(batches) bytes, 16-B aligned, one row
+ * of gradient sums per field (it depends on batches alone); it need not be
+ * initialised.
+ * One workgroup per field holds the weights, u and every activation in LDS, so
+ * s is at most MMPDE_DMM_CONVNET_TRAIN_MAX_S (what 160 KiB hold; 48 is the
+ * reference's Burgers resolution).  Every sum runs in a fixed order, no atomics
+ * and no memset: two calls on the same inputs give the same bits, and a field's
+ * f does not depend on its batch.  Stream-ordered, no allocation, no
+ * synchronisation.  Refused before any launch: a null or misaligned pointer,
+ * batches < 1, s < 1, workspace_bytes below the size above
+ * (MMPDE_ERR_INVALID_ARG); s > MMPDE_DMM_CONVNET_TRAIN_MAX_S, batches > 2^24
+ * (MMPDE_ERR_UNSUPPORTED).  The workspace size is 0 for batches outside 1..2^24.
+ * Added without a version step. */
+#define MMPDE_DMM_CONVNET_TRAIN_MAX_S 51
+#define MMPDE_DMM_CONVNET_TRAIN_GRADS 6833
+typedef struct {
+    const float *c0_w, *c0_b, *c1_w, *c1_b, *c2_w, *c2_b, *c3_w, *c3_b;
+} mmpde_dmm_convnet_weights;
+int64_t mmpde_dmm_convnet_train_workspace_bytes(int64_t batches);
+int mmpde_dmm_convnet_train_forward(const float *u, int64_t batches, int s,
+                                    const mmpde_dmm_convnet_weights *w, float *f, mmpde_stream_t stream);
+int mmpde_dmm_convnet_train_backward(const float *u, int64_t batches, int s,
+                                     const mmpde_dmm_convnet_weights *w, const float *d_f, float *grads,
+                                     void *workspace, int64_t workspace_bytes, mmpde_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Mesh quality of a moved mesh (reference mesh/dmm_utils.py:1162-1284,
  * evaluate_tri / evaluate), batched and per trajectory

@@ -124,6 +124,15 @@ DMM_GNN_TRAIN_GRADS = 124      # include/mmpde_hip.h MMPDE_DMM_GNN_TRAIN_GRADS
 DMM_DECODE_TRAIN_GRADS = 769   # include/mmpde_hip.h MMPDE_DMM_DECODE_TRAIN_GRADS
 
 
+class DmmConvnetWeights(ctypes.Structure):
+    """mmpde_dmm_convnet_weights: the eight tensors of the train-mode ConvNet stack (layers == 7), all required."""
+    _fields_ = [(n, _P) for n in ("c0_w", "c0_b", "c1_w", "c1_b", "c2_w", "c2_b", "c3_w", "c3_b")]
+
+
+DMM_CONVNET_TRAIN_MAX_S = 51       # include/mmpde_hip.h MMPDE_DMM_CONVNET_TRAIN_MAX_S
+DMM_CONVNET_TRAIN_GRADS = 6833     # include/mmpde_hip.h MMPDE_DMM_CONVNET_TRAIN_GRADS
+
+
 class RfProblem(ctypes.Structure):
     """mmpde_rf_problem: the tables and sample of mmpde_rf_objective."""
     _fields_ = [(n, _P) for n in ("so_x", "so_y", "so_xx", "so_xy", "so_yy", "b_x0", "b_x1", "b_y0", "b_y1",
@@ -273,6 +282,9 @@ _SIGS = {
     "mmpde_dmm_decode_train_workspace_bytes": (_I64, [_I64]),
     "mmpde_dmm_decode_train_forward": (_I, [_P, _I64, _I, _P, _P, _P, _P, _P, _P]),
     "mmpde_dmm_decode_train_backward": (_I, [_P, _I64, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mmpde_dmm_convnet_train_workspace_bytes": (_I64, [_I64]),
+    "mmpde_dmm_convnet_train_forward": (_I, [_P, _I64, _I, _P, _P, _P]),
+    "mmpde_dmm_convnet_train_backward": (_I, [_P, _I64, _I, _P, _P, _P, _P, _I64, _P]),
     "mmpde_rf_objective_workspace_bytes": (_I64, [_I64, _I64]),
     "mmpde_rf_objective": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "mmpde_sym_matvec": (_I, [_P, _P, _I, _P, _F, _P]),
@@ -316,7 +328,8 @@ def lib():
                 # an entry added without a version step (mmpde_dmm_mesh_relax, mmpde_mesh_quality, mmpde_itp_*_net,
                 # the random-feature phase's mmpde_dmm_rf_features / mmpde_rf_objective / mmpde_sym_matvec /
                 # mmpde_bfgs_update, the training jet's mmpde_dmm_jet / mmpde_dmm_jet_grad, the train-mode graph
-                # branch's mmpde_dmm_gnn_train_* / mmpde_dmm_decode_train_* in 12302)
+                # branch's mmpde_dmm_gnn_train_* / mmpde_dmm_decode_train_*, the train-mode array branch's
+                # mmpde_dmm_convnet_train_* in 12302)
                 raise HipExtensionMissing(
                     f"{LIB_PATH} (ABI {h.mmpde_version()}) does not export {name}: it was built "
                     f"from an older tree; rebuild it with __graft_entry__.build()") from None

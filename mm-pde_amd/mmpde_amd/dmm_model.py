@@ -76,7 +76,10 @@ class DenseNet(nn.Module):
 
 
 class ConvNet(nn.Module):
-    """Reference dmm_model.py:48-81 (layers == 7, the only configuration it builds)."""
+    """Reference dmm_model.py:48-81 (layers == 7, the only configuration it builds).
+    eval(): the conv and skinny-linear kernels.  train(): differentiable torch
+    ops in ``forward``; ``forward_train_hip`` is the same function on the
+    training kernels (DMM.hip_branch_train selects it)."""
 
     def __init__(self, s, layers):
         super().__init__()
@@ -105,6 +108,36 @@ class ConvNet(nn.Module):
         f = torch.flatten(x4, 1)
         f = ops.linear_rows(f, self.fc2.weight, self.fc2.bias, L.ACT_TANH)
         return ops.linear_rows(f, self.fc3.weight, self.fc3.bias, L.ACT_NONE)
+
+    def forward_train_hip(self, u):
+        """The train()-mode forward on kernels, u [B, s, s] -> [B, 512]: the four
+        convolutions, forward and backward, on ops.ConvNetTrain (one workgroup
+        per field, s <= ops.CONVNET_TRAIN_MAX_S, else NotImplementedError), fc2 /
+        fc3 on the few-row skinny kernels (ops.FewRowsMlp; above 4096 fields on
+        ops.linear_train, fc2's K zero-padded to a multiple of 8 as in
+        ItpNet.weights).  First order in the twelve tensors, none in u; no
+        library convolution or GEMM, the same bits on every run."""
+        s = u.shape[-1]
+        if u.dim() != 3 or u.shape[1] != s or s != self.s:
+            raise ValueError(f"ConvNet.forward_train_hip: u must be [B, {self.s}, {self.s}]")
+        if s > ops.CONVNET_TRAIN_MAX_S:
+            raise NotImplementedError(f"hip_branch_train: the array branch kernels take s <= {ops.CONVNET_TRAIN_MAX_S} "
+                                      f"(got {s})")
+        L.require_device(u)
+        c = self.layers
+        f = ops.ConvNetTrain.apply(u, c[0].weight, c[0].bias, c[1].weight, c[1].bias, c[2].weight, c[2].bias,
+                                   c[3].weight, c[3].bias)
+        if f.shape[1] != self.fc2.in_features:
+            raise ValueError(f"ConvNet: fc2 takes {self.fc2.in_features} inputs, the convolutions give {f.shape[1]}")
+        if u.shape[0] <= 4096:
+            return ops.FewRowsMlp.apply(f, self.fc2.weight, self.fc2.bias, self.fc3.weight, self.fc3.bias)
+        padk = -f.shape[1] % 8
+        if padk:   # x and W alike: the extra products are exact zeros
+            f = torch.nn.functional.pad(f, (0, padk)).contiguous()
+            h = ops.LinearRows.apply(f, torch.nn.functional.pad(self.fc2.weight, (0, padk)), self.fc2.bias)
+        else:
+            h = ops.linear_train(f, self.fc2)
+        return ops.linear_train(torch.tanh(h), self.fc3)
 
 
 class GNN_Layer_FS_2D(nn.Module):  # noqa: N801 - reference name
@@ -206,7 +239,7 @@ class DMM(nn.Module):
         self._pack = None
         self._grid_cache = {}
         self._rev_cache = {}
-        # train() mode, graph branch: run _branch_train on the HIP kernels (a plain attribute, not in state_dict)
+        # train() mode, either branch: run _branch_train on the HIP kernels (a plain attribute, not in state_dict)
         self.hip_branch_train = False
 
     def forward(self, u, grid, rf=False):
@@ -260,12 +293,17 @@ class DMM(nn.Module):
         mode): the graph branch's BatchNorms use batch statistics and advance
         their running statistics once per call.  nbr: graph mode only, an [N, k]
         int32 local neighbour table used instead of the kNN-35 table of
-        self.ori_grid.  With hip_branch_train the graph branch runs on the HIP
-        kernels (_branch_train_hip); the array branch ignores the flag."""
+        self.ori_grid.  With hip_branch_train the branch runs forward and
+        backward on the HIP kernels: the graph branch on _branch_train_hip, the
+        array branch on ConvNet.forward_train_hip (s <=
+        ops.CONVNET_TRAIN_MAX_S, else NotImplementedError).  Flag off: the torch
+        ops, bit for bit."""
         B = u.shape[0]
         if self.mode == "array":
             if nbr is not None:
                 raise ValueError("nbr is a graph-mode argument")
+            if self.hip_branch_train:
+                return self.branch.forward_train_hip(u)
             return self.branch(u.unsqueeze(1))
         else:
             og = torch.as_tensor(self.ori_grid).to(u.device, torch.float32).reshape(-1, 2)

@@ -27,7 +27,8 @@ What runs where:
   come from autograd exactly as in the reference; with jet=True the head's
   part of that -- phi's jet and its gradient in the branch output and the head
   parameters -- is the kernel pair mmpde_dmm_jet / mmpde_dmm_jet_grad (DMM.jet)
-  and only the branch stays torch;
+  and only the branch stays torch; with hip_branch=True the branch runs on
+  kernels as well, in both experiments (DMM._branch_train);
 * the softmax kernel smoother -- the reference's ``interpolate`` /
   ``interpolate_tri``, which materialise [queries, points] tensors with the
   value field repeated per query -- on the HIP kernel mmpde_softmax_interp,
@@ -461,11 +462,16 @@ def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_e
     of autograd three deep through out_nn; the loss, the optimisers and the
     logging are the same.  Default False: the autograd route, bit for bit.
 
-    hip_branch=True runs the train-mode graph branch (cylinder) on the HIP
-    kernels for the run (DMM.hip_branch_train, restored afterwards): the GNN
-    layers and the decoder on mmpde_dmm_gnn_train_* / mmpde_dmm_decode_train_*,
-    the BatchNorms, the embedding and output_mlp on the row kernels.  The array
-    branch (burgers) ignores it.  Default False: the torch ops, bit for bit.
+    hip_branch=True runs the train-mode branch on the HIP kernels for the run
+    (DMM.hip_branch_train, restored afterwards).  Graph branch (cylinder): the
+    GNN layers and the decoder on mmpde_dmm_gnn_train_* /
+    mmpde_dmm_decode_train_*, the BatchNorms, the embedding and output_mlp on
+    the row kernels.  Array branch (burgers): ConvNet's four convolutions,
+    forward and backward, on mmpde_dmm_convnet_train_* (one workgroup per
+    field, s <= ops.CONVNET_TRAIN_MAX_S, else NotImplementedError) and fc2 / fc3
+    on the few-row kernels.  With jet=True no library convolution or GEMM is
+    left in a draw of either experiment.  Default False: the torch ops, bit for
+    bit.
 
     Checkpoint file: 'dmm_{experiment}_epoch{N}.pt' in save_dir, one per epoch;
     reference_save_path=True writes the reference's name instead,

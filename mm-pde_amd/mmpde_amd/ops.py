@@ -1150,6 +1150,70 @@ class DmmDecodeTrain(torch.autograd.Function):
         return (d_h if ctx.needs_input_grad[0] else None, *out)
 
 
+CONVNET_TRAIN_MAX_S = 51   # include/mmpde_hip.h MMPDE_DMM_CONVNET_TRAIN_MAX_S
+
+
+def convnet_out_sizes(s: int) -> tuple[int, int]:
+    """(o1, o2): the side of ConvNet's x1..x3 planes and of its last convolution's output for an s x s field."""
+    o1 = (s - 1) // 2 + 1
+    return o1, (o1 - 1) // 2 + 1
+
+
+class ConvNetTrain(torch.autograd.Function):
+    """The convolution stack of the DMM array branch's ConvNet (dmm_model.py:65-79,
+    layers == 7) in train mode: f [B, o2^2] = flatten(tanh(c3(tanh(x1 +
+    c2(tanh(c1(x1))))))) with x1 = tanh(c0(u)), on
+    mmpde_dmm_convnet_train_forward / _backward.  u [B, s, s] (s <=
+    CONVNET_TRAIN_MAX_S), then weight, bias of the four convolutions.  Gradients
+    for the eight tensors; u is data.  Only the inputs are saved -- the backward
+    recomputes the stack in LDS -- and its one workspace is a row of 6833 sums
+    per field.  Deterministic."""
+
+    @staticmethod
+    def forward(ctx, u, *params):
+        L.require_device(u, *params)
+        if u.dim() != 3 or u.shape[1] != u.shape[2] or len(params) != 8:
+            raise ValueError("ConvNetTrain: u [B, s, s] and the eight tensors of the four convolutions")
+        shapes = [(8, 1, 5, 5), (8,), (16, 8, 5, 5), (16,), (8, 16, 5, 5), (8,), (1, 8, 5, 5), (1,)]
+        if [tuple(t.shape) for t in params] != shapes:
+            raise ValueError("ConvNetTrain: the convolutions of ConvNet(layers == 7) only")
+        B, s = u.shape[0], u.shape[1]
+        if s > CONVNET_TRAIN_MAX_S:
+            raise NotImplementedError(f"ConvNetTrain: the kernels hold a field's whole state in LDS and take s <= "
+                                      f"{CONVNET_TRAIN_MAX_S} (got {s})")
+        u = L.f32c(u)
+        ws = [L.f32c(t) for t in params]
+        o2 = convnet_out_sizes(s)[1]
+        f = torch.empty((B, o2 * o2), dtype=torch.float32, device=u.device)
+        wp = L.DmmConvnetWeights(*[t.data_ptr() for t in ws])
+        L.check(L.lib().mmpde_dmm_convnet_train_forward(L.ptr(u), B, s, ctypes.byref(wp), L.ptr(f),
+                                                        L.stream(u.device)), "mmpde_dmm_convnet_train_forward")
+        ctx.save_for_backward(u, *ws)
+        ctx.shapes = shapes
+        return f
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_f):
+        u, *ws = ctx.saved_tensors
+        d_f = L.f32c(d_f)
+        B, s = u.shape[0], u.shape[1]
+        dev = u.device
+        grads = torch.empty((L.DMM_CONVNET_TRAIN_GRADS,), dtype=torch.float32, device=dev)
+        nb = L.lib().mmpde_dmm_convnet_train_workspace_bytes(B)
+        wk = torch.empty((nb // 4,), dtype=torch.float32, device=dev)
+        wp = L.DmmConvnetWeights(*[t.data_ptr() for t in ws])
+        L.check(L.lib().mmpde_dmm_convnet_train_backward(L.ptr(u), B, s, ctypes.byref(wp), L.ptr(d_f), L.ptr(grads),
+                                                         L.ptr(wk), nb, L.stream(dev)),
+                "mmpde_dmm_convnet_train_backward")
+        out, o = [], 0
+        for j, shp in enumerate(ctx.shapes):
+            cnt = math.prod(shp)
+            out.append(grads[o:o + cnt].view(shp) if ctx.needs_input_grad[1 + j] else None)
+            o += cnt
+        return (None, *out)
+
+
 class FewRowsMlp(torch.autograd.Function):
     """A tanh MLP (tanh on all but the last Linear) over a few rows in train
     mode -- the DMM graph branch's output_mlp at M = B trajectories, [B, N] ->
@@ -1202,6 +1266,7 @@ class FewRowsMlp(torch.autograd.Function):
             wt = torch.empty((k, n), dtype=torch.float32, device=dev)
             L.check(lib.mmpde_transpose(L.ptr(w), n, k, k, L.ptr(wt), n, st), "mmpde_transpose")
             dx = linear_skinny(g, wt)
+            del wt          # stream-ordered: the next layer's dw and W^T may take its place
             if layer > 0:   # the layer's input is the previous layer's tanh output
                 L.check(lib.mmpde_tanh_bwd(L.ptr(dx), L.ptr(xin), dx.numel(), L.ptr(dx), st), "mmpde_tanh_bwd")
             g = dx

@@ -1,15 +1,15 @@
 """One draw of DMM training's objective + backward at the reference's Adam shape
 (--batch_size_x_adam 120 x --batch_size_u_adam 160: 19 200 interior rows and four
-sides of 30 rows per field), with the train-mode graph branch on torch ops
+sides of 30 rows per field), with the train-mode branch on torch ops
 (hip_branch off) and on the HIP kernels (hip_branch on), for jet=False and
 jet=True: hipEvent means over R draws after 3 warm-ups, the routes alternated in
 one process, every measurement twice (the run-to-run spread), and the peak
 device memory each route allocates above what is resident before the call; then
 one train-mode DMM.rf_features call on the interior rows, off and on, and the
-layer's workspace.  Synthetic fields, one sample drawn once and reused; cy
-(graph branch) and burgers (array branch, which ignores the flag), one JSON line
-each.
-    python tools/dmm_branch_time.py [--reps R] [--bx 120] [--bu 160] [--out FILE]
+kernels' workspaces.  Synthetic fields, one sample drawn once and reused; cy
+(graph branch: the GNN layer and decoder kernels) and burgers (array branch: the
+ConvNet kernels), one JSON line each.
+    python tools/dmm_branch_time.py [--reps R] [--bx 120] [--bu 160] [--kinds cy,burgers] [--out FILE]
 --out appends the lines to FILE (default profiles/dmm_branch_times.txt)."""
 import argparse
 import json
@@ -30,6 +30,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--bx", type=int, default=120)
 ap.add_argument("--bu", type=int, default=160)
+ap.add_argument("--kinds", default="cy,burgers")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dmm_branch_times.txt"))
 args = ap.parse_args()
 
@@ -64,7 +65,7 @@ def peak_mb(fn):
 
 
 dev = torch.device("cuda:0")
-for kind in ("cy", "burgers"):
+for kind in args.kinds.split(","):
     pde, _, _, _, dmm, _ = build_models(kind, seed=3)
     dmm.to(dev).train()
     Tn = 6
@@ -112,6 +113,8 @@ for kind in ("cy", "burgers"):
         n = pde.ori_grid.shape[0]
         rec["layer_workspace_MB"] = round(L.lib().mmpde_dmm_gnn_train_workspace_bytes(args.bu, n, 35) / 2 ** 20, 1)
         rec["decoder_workspace_MB"] = round(L.lib().mmpde_dmm_decode_train_workspace_bytes(args.bu * n) / 2 ** 20, 2)
+    else:
+        rec["convnet_workspace_MB"] = round(L.lib().mmpde_dmm_convnet_train_workspace_bytes(args.bu) / 2 ** 20, 2)
     dmm.hip_branch_train = False
     emit(rec)
     del dmm, sample
