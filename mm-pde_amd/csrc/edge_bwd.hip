@@ -506,9 +506,15 @@ __global__ __launch_bounds__(512, 1) void edge_bwd_f16_kernel(EdgeBwdF16Args p) 
                 for (int i = 0; i < 8; ++i)
                     mk[i] = mlds[(16 * (i >> 2) + 4 * g + (i & 3)) * MLS + 4 * e + (wave >> 1)];
             }
+            // db2: the slot's 8 rows as a tree, one add per slot into the running sum
+            // (added one by one they made a chain of 8 k terms per tile, 504 at
+            // k = 63: 5 x the fp32 kernel's db2 error at n = 64, which adds 4 rows
+            // at a time over 16-row tiles)
+            float dbs[2];
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb) {
                 _Float16 hv[4], lv[4];
+                float vq[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int rr = 16 * rb + 4 * g + q;
@@ -516,7 +522,7 @@ __global__ __launch_bounds__(512, 1) void edge_bwd_f16_kernel(EdgeBwdF16Args p) 
                                              : acc[rb][q] * un1 + bias > 0.0f;
                     const bool on = e < (MASK ? dgv[MASK ? 4 * rb + q : 0] : dg[rr]) && z2pos;
                     const float v = on ? (MASK ? gmv[MASK ? 4 * rb + q : 0] : gms[rr * FAW + col]) : 0.0f;
-                    db += v;
+                    vq[q] = v;
                     split1(v * sg, hv[q], lv[q]);
                     if (!MASK) {
                         gr[0][rr * FAS + col] = hv[q];
@@ -528,7 +534,9 @@ __global__ __launch_bounds__(512, 1) void edge_bwd_f16_kernel(EdgeBwdF16Args p) 
                 const int go = col * FCS + 8 * ((2 * rb + (g >> 1)) ^ gsw(col)) + 4 * (g & 1);
                 *(half4 *)&gt[0][go] = (half4){hv[0], hv[1], hv[2], hv[3]};
                 *(half4 *)&gt[1][go] = (half4){lv[0], lv[1], lv[2], lv[3]};
+                dbs[rb] = (vq[0] + vq[1]) + (vq[2] + vq[3]);
             }
+            db += dbs[0] + dbs[1];
         };
         // ---- P3 of slot e: gm1 -> gz1 (column kk = col); this wave's dW2 tiles
         // With `next`, P1 of slot e + 1 (the other buffer) goes in front of
