@@ -486,7 +486,30 @@ int mmpde_batch_norm_rows_train(const float *x, const float *res, int64_t n, int
                                 const float *bias, float eps, float factor, float *running_mean,
                                 float *running_var, float *y, float *stats, float *workspace,
                                 int64_t workspace_bytes, mmpde_stream_t stream);
-/* Its backward: dx = w invstd (dy - mean(dy) - xhat mean(dy xhat)) (the input
+/* The same forward over S segments of n consecutive rows each, x (+ res) and
+ * y [S n, C], every segment a batch of its own (DMM.mesh_fields: the graph
+ * branch of K fields, each field normalised with its own statistics, as the
+ * reference's per-field evaluation in train() mode, mesh/dmm_utils.py:1162-1232).
+ * stats [S, 4 C]: row s as mmpde_batch_norm_rows_train lays out its [4 C].
+ * running_mean / running_var (nullable) are advanced S times in segment order,
+ * r <- factor * (mean_s, unbiased var_s) + (1 - factor) * r, one factor for all
+ * segments.  Segment s of y, row s of stats and the final running statistics
+ * are bitwise those of S consecutive mmpde_batch_norm_rows_train calls on the
+ * segments: the same kernels' code with the segment on the grid's y axis, the
+ * row partition taken from n, and one thread per channel walking the segments
+ * for the running statistics.  Forward only.  Fixed-order sums, no atomics, no
+ * memset; stream-ordered, capturable.
+ * Refused with MMPDE_ERR_INVALID_ARG before any launch: x, y, stats or
+ * workspace null; S < 1 or S > 65535; n < 1; C < 1, C % 4 != 0 or C > 1024;
+ * x, res, y, stats or workspace not 16-byte aligned; workspace_bytes below
+ * mmpde_batch_norm_rows_train_segments_workspace_bytes(S, n, C) =
+ * S * (mmpde_batch_norm_rows_workspace_bytes(n, C) + 4 C). */
+int64_t mmpde_batch_norm_rows_train_segments_workspace_bytes(int64_t S, int64_t n, int C);
+int mmpde_batch_norm_rows_train_segments(const float *x, const float *res, int64_t S, int64_t n, int C,
+                                         const float *weight, const float *bias, float eps, float factor,
+                                         float *running_mean, float *running_var, float *y, float *stats,
+                                         float *workspace, int64_t workspace_bytes, mmpde_stream_t stream);
+/* mmpde_batch_norm_rows_train's backward: dx = w invstd (dy - mean(dy) - xhat mean(dy xhat)) (the input
  * gradient of x and of res alike), dweight = sum dy xhat, dbias = sum dy
  * (both nullable), from the forward's stats. */
 int mmpde_batch_norm_rows_backward(const float *x, const float *res, const float *dy, int64_t n, int C,

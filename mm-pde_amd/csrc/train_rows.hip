@@ -14,7 +14,9 @@
 //    GNN_Layer_FS_2D.forward (norm(h + upd), gnn_2d.py:69) fused in: batch
 //    statistics (per-thread Welford, Chan merges in a fixed order), running
 //    statistics update, the normalisation; backward with the two channel sums
-//    and the elementwise input gradient.
+//    and the elementwise input gradient.  The forward also over S row segments,
+//    each a batch of its own (the DMM's per-field evaluation, mesh/
+//    dmm_utils.py:1162-1232): the same block functions, the segment on grid.y.
 //
 // Every sum runs in a fixed order (no atomics): results are deterministic.
 #include "common.hpp"
@@ -267,7 +269,9 @@ __device__ __forceinline__ void chan_merge(float &na, float &ma, float &Ma, floa
     na = nn;
 }
 
-__global__ __launch_bounds__(256) void bn_stats_partial_kernel(BnRowsArgs p) {
+// The partial of workgroup blockIdx.x over its rows of x (+ res) [p.n, p.C], written to row blockIdx.x of part.
+__device__ __forceinline__ void bn_stats_partial_block(const BnRowsArgs &p, const float *x, const float *res,
+                                                       float *part) {
     __shared__ float sm[256 * 4], sM[256 * 4], sc[256];
     const int C4 = p.C >> 2, RG = 256 / C4;
     const int tid = threadIdx.x, rg = tid / C4, c4 = tid - rg * C4;
@@ -276,8 +280,8 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(BnRowsArgs p) {
     float m[4] = {0.0f, 0.0f, 0.0f, 0.0f}, M[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (rg < RG) {
         for (int64_t r = r0 + rg; r < r1; r += RG) {
-            float4 v = ld4(p.x + r * p.C + 4 * c4);
-            if (p.res) v = add4(v, ld4(p.res + r * p.C + 4 * c4));
+            float4 v = ld4(x + r * p.C + 4 * c4);
+            if (res) v = add4(v, ld4(res + r * p.C + 4 * c4));
             cnt += 1.0f;
             const float inv = 1.0f / cnt;
             const float vv[4] = {v.x, v.y, v.z, v.w};
@@ -309,21 +313,46 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(BnRowsArgs p) {
             }
             n0 = na + nb;
         }
-        float *pp = p.part + (int64_t)blockIdx.x * (2 * p.C + 4);
+        float *pp = part + (int64_t)blockIdx.x * (2 * p.C + 4);
         if (c4 == 0) pp[0] = n0;
         *(float4 *)&pp[4 + 4 * c4] = make_float4(m[0], m[1], m[2], m[3]);
         *(float4 *)&pp[4 + p.C + 4 * c4] = make_float4(M[0], M[1], M[2], M[3]);
     }
 }
 
-// Per channel (one workgroup each): merge the G partials -- thread t walks
-// g = t, t + 256, ... in order, then a fixed LDS tree; mean, invstd (saved for
-// the backward), the affine a = w invstd, c = b - mean a, and the running
-// statistics (torch: r = (1 - f) r + f stat, the variance unbiased).
-__global__ __launch_bounds__(256) void bn_stats_final_kernel(const float *__restrict__ part, int G, int C,
-                                                             float eps, float factor, const float *__restrict__ w,
-                                                             const float *__restrict__ b, float *__restrict__ rmean,
-                                                             float *__restrict__ rvar, float *__restrict__ stats) {
+__global__ __launch_bounds__(256) void bn_stats_partial_kernel(BnRowsArgs p) {
+    bn_stats_partial_block(p, p.x, p.res, p.part);
+}
+
+// Segment blockIdx.y of S segments of p.n rows each: its partials are rows [blockIdx.y G, + G) of part.
+__global__ __launch_bounds__(256) void bn_stats_partial_segments_kernel(BnRowsArgs p) {
+    const int64_t s = blockIdx.y, off = s * p.n * p.C;
+    bn_stats_partial_block(p, p.x + off, p.res ? p.res + off : nullptr,
+                           p.part + s * gridDim.x * (int64_t)(2 * p.C + 4));
+}
+
+struct BnChannelStat {
+    float n, mean, M2, var;  // rows, batch mean, sum of squared deviations, biased variance
+};
+
+// r <- factor stat + (1 - factor) r, the one expression of every running-statistics update here.  The rounding is
+// spelled out -- (1 - factor) r rounded, then one fma -- so that no kernel's contraction can choose the other product.
+__device__ __forceinline__ float bn_running(float factor, float stat, float r) {
+    return __fmaf_rn(factor, stat, __fmul_rn(1.0f - factor, r));
+}
+__device__ __forceinline__ float bn_unbiased(const BnChannelStat &q) {
+    return q.n > 1.0f ? q.M2 / (q.n - 1.0f) : q.var;
+}
+
+// Per channel (one workgroup each, channel blockIdx.x of one batch): merge the G
+// partials -- thread t walks g = t, t + 256, ... in order, then a fixed LDS
+// tree; mean, invstd (saved for the backward), the affine a = w invstd, c = b -
+// mean a into stats.  True on the one thread that holds q, from which the
+// kernels take the running statistics (torch: r = (1 - f) r + f stat, the
+// variance unbiased).
+__device__ __forceinline__ bool bn_stats_final_block(const float *__restrict__ part, int G, int C, float eps,
+                                                     const float *__restrict__ w, const float *__restrict__ b,
+                                                     float *__restrict__ stats, BnChannelStat &q) {
     __shared__ float sn[256], sm[256], sM[256];
     const int c = blockIdx.x, t = threadIdx.x;
     const int64_t stride = 2 * C + 4;
@@ -345,7 +374,7 @@ __global__ __launch_bounds__(256) void bn_stats_final_kernel(const float *__rest
         }
         __syncthreads();
     }
-    if (t != 0) return;
+    if (t != 0) return false;
     const float var = Ma / na;
     const float invstd = 1.0f / sqrtf(var + eps);
     const float a = w ? w[c] * invstd : invstd;
@@ -353,14 +382,57 @@ __global__ __launch_bounds__(256) void bn_stats_final_kernel(const float *__rest
     stats[C + c] = invstd;
     stats[2 * C + c] = a;
     stats[3 * C + c] = (b ? b[c] : 0.0f) - ma * a;
-    if (rmean) rmean[c] = factor * ma + (1.0f - factor) * rmean[c];
-    if (rvar) rvar[c] = factor * (na > 1.0f ? Ma / (na - 1.0f) : var) + (1.0f - factor) * rvar[c];
+    q = BnChannelStat{na, ma, Ma, var};
+    return true;
+}
+
+__global__ __launch_bounds__(256) void bn_stats_final_kernel(const float *__restrict__ part, int G, int C,
+                                                             float eps, float factor, const float *__restrict__ w,
+                                                             const float *__restrict__ b, float *__restrict__ rmean,
+                                                             float *__restrict__ rvar, float *__restrict__ stats) {
+    BnChannelStat q;
+    if (!bn_stats_final_block(part, G, C, eps, w, b, stats, q)) return;
+    const int c = blockIdx.x;
+    if (rmean) rmean[c] = bn_running(factor, q.mean, rmean[c]);
+    if (rvar) rvar[c] = bn_running(factor, bn_unbiased(q), rvar[c]);
+}
+
+// Segment blockIdx.y: stats row blockIdx.y; its unbiased variance goes to uvar [S, C] for the running walk.
+__global__ __launch_bounds__(256) void bn_stats_final_segments_kernel(const float *__restrict__ part, int G, int C,
+                                                                      float eps, const float *__restrict__ w,
+                                                                      const float *__restrict__ b,
+                                                                      float *__restrict__ uvar,
+                                                                      float *__restrict__ stats) {
+    const int64_t s = blockIdx.y;
+    BnChannelStat q;
+    if (!bn_stats_final_block(part + s * G * (int64_t)(2 * C + 4), G, C, eps, w, b, stats + s * 4 * C, q)) return;
+    uvar[s * C + blockIdx.x] = bn_unbiased(q);
+}
+
+// The running statistics after the S segments, one after the other in segment order: one thread per channel
+// (the chain is serial; its loads are not).
+__global__ __launch_bounds__(256) void bn_running_segments_kernel(const float *__restrict__ stats,
+                                                                  const float *__restrict__ uvar, int S, int C,
+                                                                  float factor, float *__restrict__ rmean,
+                                                                  float *__restrict__ rvar) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    if (rmean) {
+        float r = rmean[c];
+        for (int s = 0; s < S; ++s) r = bn_running(factor, stats[(int64_t)s * 4 * C + c], r);
+        rmean[c] = r;
+    }
+    if (rvar) {
+        float r = rvar[c];
+        for (int s = 0; s < S; ++s) r = bn_running(factor, uvar[(int64_t)s * C + c], r);
+        rvar[c] = r;
+    }
 }
 
 // y = (x + res) a + c
-__global__ __launch_bounds__(256) void bn_apply_kernel(const float *__restrict__ x, const float *__restrict__ res,
-                                                       int64_t n4, int C4, const float *__restrict__ stats, int C,
-                                                       float *__restrict__ y) {
+__device__ __forceinline__ void bn_apply_block(const float *__restrict__ x, const float *__restrict__ res,
+                                               int64_t n4, int C4, const float *__restrict__ stats, int C,
+                                               float *__restrict__ y) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         const int c = 4 * (int)(i % C4);
         float4 v = ((const float4 *)x)[i];
@@ -369,6 +441,21 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float *__restrict__
         ((float4 *)y)[i] = make_float4(fmaf(v.x, a.x, s.x), fmaf(v.y, a.y, s.y), fmaf(v.z, a.z, s.z),
                                        fmaf(v.w, a.w, s.w));
     }
+}
+
+__global__ __launch_bounds__(256) void bn_apply_kernel(const float *__restrict__ x, const float *__restrict__ res,
+                                                       int64_t n4, int C4, const float *__restrict__ stats, int C,
+                                                       float *__restrict__ y) {
+    bn_apply_block(x, res, n4, C4, stats, C, y);
+}
+
+// Segment blockIdx.y (n4 float4s each) with its own row of stats.
+__global__ __launch_bounds__(256) void bn_apply_segments_kernel(const float *__restrict__ x,
+                                                                const float *__restrict__ res, int64_t n4, int C4,
+                                                                const float *__restrict__ stats, int C,
+                                                                float *__restrict__ y) {
+    const int64_t s = blockIdx.y, off = s * n4 * 4;
+    bn_apply_block(x + off, res ? res + off : nullptr, n4, C4, stats + s * 4 * C, C, y + off);
 }
 
 // backward partials: sum dy and sum dy (x - mean) per channel
@@ -567,6 +654,39 @@ extern "C" int mmpde_batch_norm_rows_train(const float *x, const float *res, int
     const int64_t n4 = n * C / 4;
     const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(n4, 256), (int64_t)8 * device_cus());
     hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks), dim3(256), 0, st, x, res, n4, C / 4, stats, C, y);
+    MMPDE_RET_LAUNCH();
+    return MMPDE_OK;
+}
+
+extern "C" int64_t mmpde_batch_norm_rows_train_segments_workspace_bytes(int64_t S, int64_t n, int C) {
+    if (S <= 0 || n <= 0 || C <= 0) return 0;
+    return S * (mmpde_batch_norm_rows_workspace_bytes(n, C) + (int64_t)C * 4);
+}
+
+extern "C" int mmpde_batch_norm_rows_train_segments(const float *x, const float *res, int64_t S, int64_t n, int C,
+                                                    const float *weight, const float *bias, float eps, float factor,
+                                                    float *running_mean, float *running_var, float *y, float *stats,
+                                                    float *workspace, int64_t workspace_bytes,
+                                                    mmpde_stream_t stream) {
+    MMPDE_REQUIRE(x && y && stats && workspace && S > 0 && S <= 65535 && n > 0 && C > 0 && C % 4 == 0 && C <= 1024);
+    MMPDE_REQUIRE(((((uintptr_t)x | (uintptr_t)res | (uintptr_t)y | (uintptr_t)stats | (uintptr_t)workspace)) & 15) == 0);
+    MMPDE_REQUIRE(workspace_bytes >= mmpde_batch_norm_rows_train_segments_workspace_bytes(S, n, C));
+    // the row partition of one segment, as mmpde_batch_norm_rows_train takes it for n rows
+    const int64_t G0 = row_blocks(n, 64);
+    const int64_t per = (n + G0 - 1) / G0, G = (n + per - 1) / per;
+    float *uvar = workspace + S * G * (2 * C + 4);
+    BnRowsArgs p{x, res, nullptr, n, C, per, nullptr, workspace};
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(bn_stats_partial_segments_kernel, dim3((unsigned)G, (unsigned)S), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(bn_stats_final_segments_kernel, dim3((unsigned)C, (unsigned)S), dim3(256), 0, st, workspace,
+                       (int)G, C, eps, weight, bias, uvar, stats);
+    if (running_mean || running_var)
+        hipLaunchKernelGGL(bn_running_segments_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, stats,
+                           uvar, (int)S, C, factor, running_mean, running_var);
+    const int64_t n4 = n * C / 4;
+    const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(n4, 256), (int64_t)8 * device_cus());
+    hipLaunchKernelGGL(bn_apply_segments_kernel, dim3(blocks, (unsigned)S), dim3(256), 0, st, x, res, n4, C / 4,
+                       stats, C, y);
     MMPDE_RET_LAUNCH();
     return MMPDE_OK;
 }

@@ -223,6 +223,9 @@ _SIGS = {
     "mmpde_rows_grad_weight": (_I, [_P, _I64, _I64, _I, _P, _I64, _I, _P, _P, _P, _I64, _P]),
     "mmpde_batch_norm_rows_workspace_bytes": (_I64, [_I64, _I]),
     "mmpde_batch_norm_rows_train": (_I, [_P, _P, _I64, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _I64, _P]),
+    "mmpde_batch_norm_rows_train_segments_workspace_bytes": (_I64, [_I64, _I64, _I]),
+    "mmpde_batch_norm_rows_train_segments": (_I, [_P, _P, _I64, _I64, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _I64,
+                                                  _P]),
     "mmpde_batch_norm_rows_backward": (_I, [_P, _P, _P, _I64, _I, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "mmpde_rgemm": (_I, [_P, _P]),
     "mmpde_rgemm_tn_workspace_bytes": (_I64, [_I64, _I, _I]),

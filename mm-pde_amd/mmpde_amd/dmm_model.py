@@ -25,6 +25,9 @@ reference's computation as differentiable device torch ops -- BatchNorm on
 batch statistics, twice differentiable in the grid (the Monge-Ampere loss
 takes d2 phi / d xi2 through autograd) -- with the fixed grid's kNN-35 graph
 from the HIP kernel and the mean aggregation over its fixed in-degree.
+``DMM.mesh_fields`` is the moved mesh of K fields, each a batch of its own to
+the BatchNorms, in either mode and without autograd (DMM training's per-epoch
+evaluation, K fields per call).
 """
 from __future__ import annotations
 
@@ -323,7 +326,7 @@ class DMM(nn.Module):
             h, _ = self.decoding_mlp(h)
             return self.output_mlp(h.reshape(B, -1))
 
-    def _branch_train_hip(self, u, og, nbr):
+    def _branch_train_hip(self, u, og, nbr, segments=1):
         """_branch_train's graph branch on kernels, forward and backward: the
         embedding on the row kernels (ops.linear_train, ops.batch_norm_rows),
         every GNN layer's update on ops.DmmGnnLayerTrain with its residual and
@@ -331,7 +334,11 @@ class DMM(nn.Module):
         output_mlp on the few-row skinny kernels (ops.FewRowsMlp; above 4096
         trajectories on ops.linear_train).  The same modules' BatchNorms advance
         in the same order as on the torch route; no per-edge tensor and no
-        library GEMM."""
+        library GEMM.  segments = B (mesh_fields; forward only, under
+        torch.no_grad()): every BatchNorm takes each trajectory's N rows as a batch
+        of its own and advances B times, in trajectory order, as B calls of one
+        trajectory each would (ops.batch_norm_rows(segments=)); nothing else in
+        the sequence mixes trajectories."""
         if self.hidden_features != 4:
             raise NotImplementedError("hip_branch_train: the graph branch kernels take hidden_features == 4 only "
                                       f"(got {self.hidden_features})")
@@ -341,14 +348,14 @@ class DMM(nn.Module):
         uf = u.float().reshape(-1)
         e = self.embedding_mlp
         x3 = torch.cat((uf[:, None], og.repeat(B, 1)), -1)
-        h = ops.batch_norm_rows(e[1], ops.linear_train(x3, e[0]))
-        h = ops.batch_norm_rows(e[4], ops.linear_train(torch.tanh(h), e[3]))
+        h = ops.batch_norm_rows(e[1], ops.linear_train(x3, e[0]), segments=segments)
+        h = ops.batch_norm_rows(e[4], ops.linear_train(torch.tanh(h), e[3]), segments=segments)
         for g in self.gnn_layers:
             upd = ops.DmmGnnLayerTrain.apply(
                 h, uf, og, nbr, rev, g.message_net_1[0].weight, g.message_net_1[0].bias, g.message_net_2[0].weight,
                 g.message_net_2[0].bias, g.update_net_1[0].weight, g.update_net_1[0].bias, g.update_net_2[0].weight,
                 g.update_net_2[0].bias)
-            h = ops.batch_norm_rows(g.norm.module, upd, res=h)
+            h = ops.batch_norm_rows(g.norm.module, upd, res=h, segments=segments)
         d = self.decoding_mlp.layers
         dec = ops.DmmDecodeTrain.apply(h, d[0].weight, d[0].bias, d[1].weight, d[1].bias)
         o = self.output_mlp
@@ -626,6 +633,47 @@ class DMM(nn.Module):
                 L.ptr(u), L.ptr(xi), B, N, ctypes.byref(bp), ctypes.byref(hd), hc,
                 L.ptr(workspace), L.ptr(out), st), "mmpde_dmm_mesh_array")
         return out
+
+    def mesh_fields(self, u: torch.Tensor, xi: torch.Tensor) -> torch.Tensor:
+        """The moved mesh xi + grad(phi) of each of the K fields of u, every field
+        treated as a batch of its own: what K calls with one field each give
+        (the reference's per-epoch evaluation, mesh/dmm_utils.py:1162-1284, which
+        runs the model in whatever mode training left it in).  u, xi as for
+        mesh; returns [K * N, 2] fp32, under torch.no_grad().
+        eval(): mesh(u, xi).
+        train(): the branch on the training kernels -- array mode
+        ConvNet.forward_train_hip for s <= ops.CONVNET_TRAIN_MAX_S and the torch
+        ConvNet above (no BatchNorm there: a batch of K is K batches of one);
+        graph mode _branch_train_hip's sequence on self.ori_grid with every
+        BatchNorm over K row segments (ops.batch_norm_rows(segments=K)): each
+        field normalised with its own statistics, the running statistics
+        advanced K times in field order and num_batches_tracked by K.  Graph
+        mode needs hidden_features == 4 (NotImplementedError otherwise).  grad(phi)
+        is the head's closed form (ops.dmm_jet, first order) at xi repeated K
+        times; the head has no BatchNorm."""
+        L.require_device(u, xi)
+        if not self.training:
+            with torch.no_grad():
+                return self.mesh(u, xi)
+        xi = L.f32c(xi).reshape(-1, 2)
+        K = u.shape[0]
+        with torch.no_grad():
+            if self.mode == "array":
+                if self.branch.s <= ops.CONVNET_TRAIN_MAX_S:
+                    branch = self.branch.forward_train_hip(L.f32c(u))
+                else:
+                    branch = self.branch(u.float().unsqueeze(1))
+            else:
+                if self.hidden_features != 4:
+                    raise NotImplementedError("mesh_fields: the graph branch kernels take hidden_features == 4 only "
+                                              f"(got {self.hidden_features})")
+                og = torch.as_tensor(self.ori_grid).to(u.device, torch.float32).reshape(-1, 2).contiguous()
+                branch = self._branch_train_hip(u, og, self.grid_nbr(og), segments=K)
+            hd, keep = self._head_params()
+            rows = xi.repeat(K, 1)
+            jet = ops.dmm_jet(branch, rows, hd, self.out_nn.layers[1].bias, second_order=False)
+            del keep
+            return rows + torch.stack((jet.phi_x, jet.phi_y), dim=-1)
 
     # ----------------------------------------------------------------- the mesh Jacobian
     def hess_cache(self, xi: torch.Tensor, workspace: torch.Tensor | None = None) -> torch.Tensor:

@@ -36,7 +36,11 @@ What runs where:
   the monitor's uniform-grid derivatives of interpolate_tri (the reference's
   autograd.grad with grad_outputs = 1) are that VJP directly;
 * sampling follows the reference's numpy RNG calls one for one (np.random
-  uniform / choice), so a seeded run draws the same points.
+  uniform / choice), so a seeded run draws the same points;
+* evaluate / evaluate_tri after every epoch: the reference's loop of one field
+  per model call by default; with batch=K (train_MA_res's eval_batch) K fields
+  per call on DMM.mesh_fields, ops.mesh_monitor and ops.mesh_quality
+  (_evaluate_batched), the same fields in the same order.
 
 ``train_MA_res`` keeps the reference's signature, optimisers (Adam with weight
 decay + MultiStepLR [100, 150]; LBFGS with tolerances -1 + MultiStepLR
@@ -435,7 +439,7 @@ def random_feature_epoch(model, args, all_u, device, dense=None):
 # --------------------------------------------------------------------------- training
 def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_epoch_lbfgs, device,
                  save_dir=None, evaluate_every=1, reference_save_path=False, jet: bool = False,
-                 hip_branch: bool = False):  # noqa: N802
+                 hip_branch: bool = False, eval_batch: int | None = None):  # noqa: N802
     """dmm_utils.py:391-1095: n_epoch_adam
     epochs of Adam then n_epoch_lbfgs of LBFGS, each epoch max(1, train_sample_grid
     T / (bx bu)) draws of fresh samples; per epoch the equation residual of the
@@ -473,6 +477,10 @@ def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_e
     left in a draw of either experiment.  Default False: the torch ops, bit for
     bit.
 
+    eval_batch=K passes batch=K to the four evaluate / evaluate_tri calls that
+    end an epoch (K fields per model call on the kernels instead of one; see
+    their docstrings for the limits).  Default None: the per-field loop.
+
     Checkpoint file: 'dmm_{experiment}_epoch{N}.pt' in save_dir, one per epoch;
     reference_save_path=True writes the reference's name instead,
     '{experiment}/{datetime}_{rf}_bound{loss_bound_rf}_..._{gamma_adam}'
@@ -486,17 +494,18 @@ def train_MA_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_e
     init_mesh LBFGS phase runs backward like every other phase and logs 0 for
     the convexity loss and None for LHS (tests/test_gpu_dmm_train.py
     ::test_init_mesh_lbfgs_phase_trains)."""
+    _check_batch(eval_batch)
     prev = getattr(model, "hip_branch_train", False)
     model.hip_branch_train = bool(hip_branch)
     try:
         return _train_ma_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_epoch_lbfgs, device,
-                             save_dir, evaluate_every, reference_save_path, jet)
+                             save_dir, evaluate_every, reference_save_path, jet, eval_batch)
     finally:
         model.hip_branch_train = prev
 
 
 def _train_ma_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_epoch_lbfgs, device, save_dir,
-                  evaluate_every, reference_save_path, jet):
+                  evaluate_every, reference_save_path, jet, eval_batch=None):
     """train_MA_res's epochs (the hip_branch flag already set on the model)."""
     model.train()
     opt_adam = torch.optim.Adam(model.parameters(), lr=args.lr_adam, betas=(0.9, 0.999), eps=1e-8,
@@ -532,11 +541,11 @@ def _train_ma_res(ori_u, all_u, test_u, args, model, init_mesh, n_epoch_adam, n_
         """evaluate[_tri] when evaluate_every says so, and the checkpoint."""
         if evaluate_every and epoch % evaluate_every == 0:
             if args.experiment == "burgers":
-                tr = evaluate(model, all_u, device, epoch)
-                te = evaluate(model, test_u, device, epoch)
+                tr = evaluate(model, all_u, device, epoch, batch=eval_batch)
+                te = evaluate(model, test_u, device, epoch, batch=eval_batch)
             else:
-                tr = evaluate_tri(model, all_u[:, :, 2], all_u[0, :, :2], device, epoch)
-                te = evaluate_tri(model, test_u[:, :, 2], all_u[0, :, :2], device, epoch)
+                tr = evaluate_tri(model, all_u[:, :, 2], all_u[0, :, :2], device, epoch, batch=eval_batch)
+                te = evaluate_tri(model, test_u[:, :, 2], all_u[0, :, :2], device, epoch, batch=eval_batch)
             for k, v in zip(("train_mean", "train_std", "train_minmax"), tr):
                 log[k].append(v)
             for k, v in zip(("test_mean", "test_std", "test_minmax"), te):
@@ -634,15 +643,57 @@ def _moved(model, u, xi):
     return torch.cat((_grad(phi, x1) + x1, _grad(phi, x2) + x2), -1).detach()
 
 
-def evaluate_tri(model, u, grid, device, epoch=None):
+def _check_batch(batch):
+    if batch is not None and (not isinstance(batch, (int, np.integer)) or isinstance(batch, bool) or batch < 1):
+        raise ValueError(f"batch must be None (one field per model call) or an integer >= 1 (got {batch!r})")
+
+
+def _evaluate_batched(model, u, order, batch, xi, cells, grid=None):
+    """evaluate / evaluate_tri with batch=K: the fields u[order] in chunks of K
+    (the last one shorter), per chunk DMM.mesh_fields, ops.mesh_monitor (grid
+    None: the array form) and ops.mesh_quality on one MeshCells table; the
+    per-field (mean, std, range) stay on the device and are read back once,
+    then averaged over the fields in float64 as np.mean does."""
+    from . import ops
+
+    idx = torch.as_tensor(np.asarray(order), dtype=torch.long, device=u.device)
+    stats = torch.empty((3, idx.numel()), dtype=torch.float32, device=u.device)
+    for a in range(0, idx.numel(), batch):
+        uk = u[idx[a:a + batch]].float().contiguous()
+        k = uk.shape[0]
+        mesh = model.mesh_fields(uk, xi)
+        m, _, _ = ops.mesh_monitor(uk, grid)
+        q = ops.mesh_quality(mesh, xi, cells, m, k)
+        stats[0, a:a + k], stats[1, a:a + k], stats[2, a:a + k] = q.mean, q.std, q.range
+    return tuple(float(v) for v in stats.double().cpu().numpy().mean(axis=1))
+
+
+def evaluate_tri(model, u, grid, device, epoch=None, batch=None):
     """dmm_utils.py:1162-1232: on up to 150 random fields, the monitor at each
     moved triangle's centroid times its area (Delaunay triangles of the fixed
-    mesh), averaged: (mean, std, max - min) over triangles, mean over fields."""
+    mesh), averaged: (mean, std, max - min) over triangles, mean over fields.
+    batch None: one field per model call, the reference's loop.  batch = K >= 1
+    (ValueError below 1): the same fields in the same order (one np.random.choice
+    call either way), K per call, on DMM.mesh_fields, ops.mesh_monitor and
+    ops.mesh_quality with the Delaunay triangles of grid (_evaluate_batched);
+    every field still a batch of its own to the model's BatchNorms, which in
+    train() mode advance once per field.  Limits of that route, raised and not
+    worked around: a monitor lattice of 2 <= floor(sqrt(N)) <=
+    ops.MESH_QUALITY_MAX_N, and in train() mode a graph branch of
+    hidden_features == 4."""
     from scipy.spatial import Delaunay
 
+    _check_batch(batch)
     u = u.to(device)
     grid = grid.to(device).float()
     N = u.shape[-1]
+    if batch is not None:
+        from . import ops
+
+        grid = grid.contiguous()
+        cells = ops.MeshCells(ops.mesh_cells_delaunay(grid), N, device)
+        order = np.random.choice(u.shape[0], min(150, u.shape[0]), replace=False)
+        return _evaluate_batched(model, u, order, int(batch), grid, cells, grid)
     n = int(np.sqrt(N))
     tris = torch.from_numpy(Delaunay(grid.detach().cpu().numpy()).simplices.astype(np.int64)).to(device)
     lat = unit_lattice(n, device)
@@ -661,12 +712,26 @@ def evaluate_tri(model, u, grid, device, epoch=None):
     return tuple(float(np.mean([s[i] for s in stats])) for i in range(3))
 
 
-def evaluate(model, u, device, epoch=None):
+def evaluate(model, u, device, epoch=None, batch=None):
     """dmm_utils.py:1235-1284 (array data u [T, s, s]): the monitor at each moved
-    quadrilateral's centre times its area (product of the diagonals / 2)."""
+    quadrilateral's centre times its area (product of the diagonals / 2).
+    batch None: one field per model call, the reference's loop.  batch = K >= 1
+    (ValueError below 1): the same fields in the same order (one np.random.choice
+    call either way), K per call, on DMM.mesh_fields, ops.mesh_monitor and
+    ops.mesh_quality with the lattice quadrilaterals (_evaluate_batched).
+    Limits of that route, raised and not worked around: 2 <= s <=
+    ops.MESH_QUALITY_MAX_N, and u[b, i, j] is read as the lattice value at
+    (x_j, y_i), the orientation this function has always used."""
+    _check_batch(batch)
     s = u.shape[-1]
     xi = unit_lattice(s, device)
     u = u.to(device)
+    if batch is not None:
+        from . import ops
+
+        cells = ops.MeshCells(ops.mesh_cells_lattice(s), s * s, device)
+        order = np.random.choice(u.shape[0], u.shape[0], replace=False)
+        return _evaluate_batched(model, u, order, int(batch), xi, cells)
     _, m, _ = _alpha_m_rhs(diff_x(u) * (s - 1), diff_y(u) * (s - 1))
     stats = []
     for t in np.random.choice(u.shape[0], u.shape[0], replace=False):

@@ -772,10 +772,65 @@ class BatchNormRows(torch.autograd.Function):
         return dx, (dx if has_res else None), dw, db, None, None, None, None
 
 
-def batch_norm_rows(bn: torch.nn.BatchNorm1d, x: torch.Tensor, res: torch.Tensor | None = None) -> torch.Tensor:
+def _batch_norm_rows_segments(bn, x, res, segments: int) -> torch.Tensor:
+    """batch_norm_rows' train-mode route for segments > 1 (forward only)."""
+    params = (bn.weight, bn.bias) if torch.is_grad_enabled() else ()
+    if any(t is not None and t.requires_grad for t in (x, res, *params)):
+        raise ValueError("batch_norm_rows(segments > 1) is forward only: x and res must not require grad, and the "
+                         "module's parameters only under torch.no_grad()")
+    if x.dim() != 2 or x.shape[0] % segments or x.shape[1] % 4 or not 4 <= x.shape[1] <= 1024:
+        raise ValueError(f"batch_norm_rows(segments={segments}): x must be [segments * n, C] with C % 4 == 0, "
+                         f"C <= 1024 (got {tuple(x.shape)})")
+    n, C = x.shape[0] // segments, x.shape[1]
+    if n < 2:
+        raise ValueError("batch_norm_rows: a train-mode segment needs more than one row")
+    if res is not None and res.shape != x.shape:
+        raise ValueError("batch_norm_rows: res must have x's shape")
+    L.require_device(x, res)
+    track = bn.track_running_stats and bn.num_batches_tracked is not None
+    if track and bn.momentum is None:   # a factor per segment: the calls one after the other
+        with torch.no_grad():
+            return torch.cat([batch_norm_rows(bn, x[s * n:(s + 1) * n], None if res is None else res[s * n:(s + 1) * n])
+                              for s in range(segments)])
+    factor = 0.0
+    if track:
+        bn.num_batches_tracked.add_(segments)
+        factor = bn.momentum
+    rm = bn.running_mean if bn.track_running_stats else None
+    rv = bn.running_var if bn.track_running_stats else None
+    x = x.detach().float().contiguous()
+    res = res.detach().float().contiguous() if res is not None else None
+    w = L.f32c(bn.weight.detach()) if bn.weight is not None else None
+    b = L.f32c(bn.bias.detach()) if bn.bias is not None else None
+    dev = x.device
+    y = torch.empty_like(x)
+    stats = torch.empty((segments, 4 * C), dtype=torch.float32, device=dev)
+    nb = L.lib().mmpde_batch_norm_rows_train_segments_workspace_bytes(segments, n, C)
+    ws = torch.empty((nb // 4,), dtype=torch.float32, device=dev)
+    L.check(L.lib().mmpde_batch_norm_rows_train_segments(
+        L.ptr(x), L.ptr(res), segments, n, C, L.ptr(w), L.ptr(b), float(bn.eps), float(factor), L.ptr(rm), L.ptr(rv),
+        L.ptr(y), L.ptr(stats), L.ptr(ws), nb, L.stream(dev)), "mmpde_batch_norm_rows_train_segments")
+    return y
+
+
+def batch_norm_rows(bn: torch.nn.BatchNorm1d, x: torch.Tensor, res: torch.Tensor | None = None,
+                    segments: int = 1) -> torch.Tensor:
     """bn(x + res) for [n, C] rows: the HIP kernels in train mode (running
     statistics and num_batches_tracked advanced as nn.BatchNorm1d does), the
-    module itself in eval mode."""
+    module itself in eval mode.
+    segments = S > 1, train mode: x (+ res) is S segments of n / S consecutive
+    rows, each normalised as a batch of its own, the running statistics
+    advanced S times in segment order and num_batches_tracked by S -- what S
+    calls on the segments give, bit for bit -- in one
+    mmpde_batch_norm_rows_train_segments call.  Forward only: raises if x or
+    res requires grad, or a parameter does outside torch.no_grad(); a shape the
+    kernel does not take raises too.  momentum=None (the cumulative average, another factor for
+    every segment) takes the S calls one after the other instead.  In eval mode
+    BatchNorm acts row by row, so segments changes nothing there."""
+    if segments < 1:
+        raise ValueError(f"batch_norm_rows: segments must be >= 1 (got {segments})")
+    if segments > 1 and bn.training:
+        return _batch_norm_rows_segments(bn, x, res, segments)
     if not bn.training or x.dim() != 2 or x.shape[1] % 4 or x.shape[1] > 1024 or x.shape[0] < 2:
         return bn(x if res is None else x + res)
     factor = 0.0
